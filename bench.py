@@ -13,6 +13,14 @@ N GPUs:      python -m torch.distributed.run --nproc-per-node N ... bench.py --g
              or python bench.py --gpus N (starts the N rank processes itself)
 Ranks meet on gloo (barrier + max over ranks); each holds one HIP runtime,
 the engine library's.  Prints one JSON line (rank 0).
+
+A plain run does what the headline needs and no more: it builds the resident
+batches, warms up, times exactly --steps steps, re-checks the timed outputs
+against the batches' known answers (a fetch and a compare) and prints the
+line.  --full adds the side measurements, each a run of its own after the
+clock: the per-kernel pass and the rooflines, the product-path pipeline, the
+small-batch latency probe, the host signing-root rate and the CPU baseline.
+--dump-outputs DIR writes the last timed step's outputs as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -479,6 +487,41 @@ def batch_exact(res, b, eng):
     return bool(np.array_equal(res.agg[ok], b.group_sig[ok]))
 
 
+DUMP_BUDGET_BYTES = 63 * 1000 * 1000  # --dump-outputs: the files of one run stay under 64 MB together (float32)
+DUMP_SEED = 20240531
+
+
+def dump_outputs(path, res, rank=0):
+    """--dump-outputs: what the caller of the timed path receives for its last
+    step (BatchResult: per-partial status, per-duty status, the 96-byte
+    aggregates) as <path>/<name>.npy in float32 (every value is a small
+    integer, so the conversion is exact).  An output over the size budget is
+    written as a fixed, seeded sample of its duties and of its partials; the
+    sampled rows are written beside it (duty_index / partial_index, float64).
+    Ranks above 0 prefix their files with rank<r>_."""
+    os.makedirs(path, exist_ok=True)
+    nd, n_p = len(res.duty_status), len(res.partial_status)
+    per_duty = 4 * (96 + 1) + 8  # agg row + duty status + its index
+    per_partial = 4 + 8
+    arrays = {}
+    if nd * per_duty + n_p * per_partial > DUMP_BUDGET_BYTES:
+        rng = np.random.default_rng(DUMP_SEED)
+        kd = min(nd, (DUMP_BUDGET_BYTES * 3 // 4) // per_duty)
+        kp = min(n_p, (DUMP_BUDGET_BYTES // 4) // per_partial)
+        di = np.sort(rng.choice(nd, size=kd, replace=False))
+        pi = np.sort(rng.choice(n_p, size=kp, replace=False))
+        arrays["duty_index"] = di.astype(np.float64)
+        arrays["partial_index"] = pi.astype(np.float64)
+    else:
+        di, pi = slice(None), slice(None)
+    arrays["partial_status"] = res.partial_status[pi].astype(np.float32)
+    arrays["duty_status"] = res.duty_status[di].astype(np.float32)
+    arrays["agg"] = res.agg[di].astype(np.float32)
+    prefix = f"rank{rank}_" if rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(path, prefix + name + ".npy"), a)
+
+
 def host_side(hs, duties, wall_s):
     """The host share of the multi-context product path, timed inside the
     library (tbg_multi_host_stats): CPU time of the sub-batch builds, the
@@ -549,6 +592,8 @@ def config4_multi(args):
         ok = ds == eng.DS_OK
         exact = bool(np.array_equal(ps == eng.PS_VALID, ~b.injected) and np.array_equal(ok, b.expect_ok)
                      and np.array_equal(agg[ok], b.group_sig[ok]))
+        if args.dump_outputs:  # the last round's results, in caller order
+            dump_outputs(args.dump_outputs, eng.BatchResult(ps, ds, agg))
         return {"metric": METRIC, "value": round(args.dvs * rounds / dt, 2),
                 "unit": "DV-duties/s (n verifies + 1 aggregate each)", "n_gpus": ndev, "steps": rounds,
                 "warmup": 1, "ms_per_step": round(dt * 1e3 / rounds, 3), "higher_is_better": True,
@@ -581,8 +626,15 @@ def main():
                          "unset) N > 1 starts N rank processes itself; under one, N must equal WORLD_SIZE")
     ap.add_argument("--launch-check", action="store_true",
                     help="run only the rank plumbing (gloo barrier, max-over-ranks) and print the ranks seen")
-    ap.add_argument("--steps", type=int, default=48)
+    ap.add_argument("--steps", type=int, default=48, help="timed steps (exactly this many batches are replayed)")
     ap.add_argument("--warmup", type=int, default=16)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements after the clock: per-kernel pass and rooflines, product-path "
+                         "pipeline (--api-batches), latency probe (--latency), host signing roots, CPU baseline "
+                         "(--no-cpu / --cpu-seconds); without it those options are not used")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step (per-partial status, "
+                         "per-duty status, aggregates) as DIR/<name>.npy (float32)")
     ap.add_argument("--dvs", type=int, default=10000)
     ap.add_argument("--t", type=int, default=3)
     ap.add_argument("--n", type=int, default=4)
@@ -629,6 +681,8 @@ def main():
         args.gpus = int(ws_env) if ws_env else 1
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if ws_env is None and args.gpus > 1:
         # no launcher: this process only starts the ranks (it never touches the GPU)
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -654,6 +708,8 @@ def main():
         args.inject = 0.01 if args.workload == "config5" else 0.0
     if args.workload != "config2":
         args.api_batches = 0  # the product-path side key is measured on the headline shape
+    if not args.full:  # a plain run: the headline alone
+        args.api_batches, args.latency, args.no_cpu = 0, 0, True
 
     # The engine library is loaded first: its HIP runtime (ROCm's
     # libamdhip64.so.7) is the one the process initialises; torch comes in
@@ -736,6 +792,12 @@ def main():
         kernel_ms.update(e.replay_plan(*plan(k)))
 
     elapsed, _ = timed_steps(step_fn, args.steps, ws, sync=e.synchronize)
+    if args.dump_outputs:
+        # the last step of the timed plan: the last batch its last launch ran
+        ts, ps = plan(args.steps)
+        last = (ps[-1] or M) - 1
+        lb = batches[tickets.index(ts[-1])][last]
+        dump_outputs(args.dump_outputs, e.fetch(ts[-1] + last, lb.n_dv, len(lb.identifiers)), rank)
     # outputs of the timed replays must still be exact (every batch of every slot)
     exact_after = True
     for group, t0 in zip(batches, tickets):
@@ -763,24 +825,37 @@ def main():
     value = units / elapsed
     ms_per_step = elapsed * 1e3 / args.steps
 
-    # Per-kernel pass (untimed): one resident device batch (`merge` batches)
+    side = {}
+    # Per-kernel pass (--full, untimed): one resident device batch (`merge` batches)
     # replayed alone, an event pair around every kernel -- the exclusive
     # durations the roofline prices; the stage sums are isolated_batch_ms.
-    kp = kernel_profile(e.replay_profile(tickets[0]))
-    shape = e.shape(tickets[0])  # the shape that profiled replay ran (the whole device batch)
-    iso = {st: round(sum(kp[k][0] for k in ks if k in kp), 3) for st, ks in STAGE_KERNELS.items()}
-    iso["total"] = round(sum(v[0] for v in kp.values()), 3)
-    wm = work_model()
-    items = launch_items(batches[0], shape)
-    roofline = kernel_roofline(wm, kp, items, traffic_model(), M)
-    # the roofline is per GPU: whole-job rate / ranks against one GPU's peak
-    roofline_pipeline = pipeline_roofline(wm, value / ws, l0_state == eng.L0_PASSED, args.t, args.n,
-                                          subgroup["groups"] > 0, items) \
-        if args.workload in ("config2", "config4") else None
-    # (before api_pipeline: the load replays the resident launches)
-    lat = latency_probe(e, eng, plan(3 * M)) if args.latency and rank == 0 and args.workload == "config2" else None
-    # (reuses the engine's slots: after the replays and the isolated pass)
-    api = api_pipeline(e, eng, flat, args.inflight + 1, args.api_batches, M) if args.api_batches else None
+    kp = kernel_profile(e.replay_profile(tickets[0])) if args.full else None
+    shape = e.shape(tickets[0])  # the shape the slot's last replay ran (--full: the whole device batch)
+    if args.full:
+        iso = {st: round(sum(kp[k][0] for k in ks if k in kp), 3) for st, ks in STAGE_KERNELS.items()}
+        iso["total"] = round(sum(v[0] for v in kp.values()), 3)
+        wm = work_model()
+        items = launch_items(batches[0], shape)
+        roofline = kernel_roofline(wm, kp, items, traffic_model(), M)
+        # the roofline is per GPU: whole-job rate / ranks against one GPU's peak
+        roofline_pipeline = pipeline_roofline(wm, value / ws, l0_state == eng.L0_PASSED, args.t, args.n,
+                                              subgroup["groups"] > 0, items) \
+            if args.workload in ("config2", "config4") else None
+        # (before api_pipeline: the load replays the resident launches)
+        lat = latency_probe(e, eng, plan(3 * M)) if args.latency and rank == 0 and args.workload == "config2" else None
+        # (reuses the engine's slots: after the replays and the isolated pass)
+        api = api_pipeline(e, eng, flat, args.inflight + 1, args.api_batches, M) if args.api_batches else None
+        side = {
+            "api_pipeline": api,
+            "small_batch_latency": lat,
+            "isolated_batch_ms": iso,
+            "isolated_kernel_ms": {k: round(v[0], 4) for k, v in sorted(kp.items(), key=lambda kv: -kv[1][0])
+                                   if v[0] >= 0.05},
+            "roofline": roofline,
+            "roofline_pipeline": roofline_pipeline,
+            "cpu_baseline": None,
+            "host_signing_roots": None,
+        }
 
     result = {
         "metric": METRIC, "value": round(value, 2), "unit": "DV-duties/s (n verifies + 1 aggregate each)",
@@ -800,17 +875,10 @@ def main():
         "slot_bytes": {"device": int(slot_dev), "pinned_host": int(slot_pinned), "batches_per_slot": M},
         "kernel_ms_per_step": {k: round(v / args.steps, 3) for k, v in kernel_ms.items()},
         "pcie_inclusive_ms_first_batch": round(pcie_ms, 3),
-        "api_pipeline": api,
-        "small_batch_latency": lat,
-        "isolated_batch_ms": iso,
-        "isolated_kernel_ms": {k: round(v[0], 4) for k, v in sorted(kp.items(), key=lambda kv: -kv[1][0])
-                               if v[0] >= 0.05},
-        "roofline": roofline,
-        "roofline_pipeline": roofline_pipeline,
-        "cpu_baseline": None,
-        "host_signing_roots": None,
+        "full": bool(args.full),
+        **side,
     }
-    if rank == 0:
+    if args.full and rank == 0:
         # the host step in front of the GPU path: AttestationData -> signing
         # root (include/tbls_ssz.h), 16 threads -- must outpace `value`
         from tools.ssz_bench import run_rate

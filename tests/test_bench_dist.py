@@ -161,3 +161,57 @@ def test_batch_exact_follows_injection():
     bad_agg = agg.copy()
     bad_agg[0, 5] ^= 1
     assert not bench.batch_exact(types.SimpleNamespace(**{**vars(good), "agg": bad_agg}), b, eng)
+
+
+def test_dump_outputs_files_and_seeded_sample(tmp_path):
+    """bench.py --dump-outputs (no GPU): the last step's BatchResult is written
+    as float32 .npy files holding exactly its values; an output over the size
+    budget is written as the same seeded sample on every run, with the sampled
+    rows beside it, and the files stay under 64 MB together."""
+    import types
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(5)
+    res = types.SimpleNamespace(partial_status=rng.integers(-6, 3, size=40).astype(np.int32),
+                                duty_status=rng.integers(-25, 2, size=10).astype(np.int32),
+                                agg=rng.integers(0, 256, size=(10, 96)).astype(np.uint8))
+    d = tmp_path / "small"
+    bench.dump_outputs(str(d), res)
+    assert sorted(p.name for p in d.iterdir()) == ["agg.npy", "duty_status.npy", "partial_status.npy"]
+    for name in ("partial_status", "duty_status", "agg"):
+        a = np.load(d / (name + ".npy"))
+        assert a.dtype == np.float32
+        assert np.array_equal(a, getattr(res, name))
+    bench.dump_outputs(str(d), res, rank=1)
+    assert np.array_equal(np.load(d / "rank1_agg.npy"), res.agg)
+    # 1M duties x 4 partials: ~400 MB as float32, so a sample is written
+    nd = 1_000_000
+    big = types.SimpleNamespace(partial_status=np.arange(4 * nd, dtype=np.int32) % 3,
+                                duty_status=np.arange(nd, dtype=np.int32) % 2,
+                                agg=np.broadcast_to((np.arange(nd, dtype=np.uint32) % 251).astype(np.uint8)[:, None],
+                                                    (nd, 96)))
+    runs = []
+    for k in range(2):
+        dk = tmp_path / f"big{k}"
+        bench.dump_outputs(str(dk), big)
+        assert sum(p.stat().st_size for p in dk.iterdir()) <= 64 * 1000 * 1000
+        runs.append({p.name: np.load(p) for p in dk.iterdir()})
+    assert runs[0].keys() == runs[1].keys() == {"agg.npy", "duty_status.npy", "partial_status.npy",
+                                                "duty_index.npy", "partial_index.npy"}
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name])
+    di = runs[0]["duty_index.npy"].astype(np.int64)
+    pi = runs[0]["partial_index.npy"].astype(np.int64)
+    assert runs[0]["duty_index.npy"].dtype == np.float64 and len(np.unique(di)) == len(di) > 100_000
+    assert np.array_equal(runs[0]["agg.npy"], big.agg[di]) and runs[0]["agg.npy"].dtype == np.float32
+    assert np.array_equal(runs[0]["duty_status.npy"], big.duty_status[di])
+    assert np.array_equal(runs[0]["partial_status.npy"], big.partial_status[pi])
+
+
+def test_full_and_dump_outputs_are_options():
+    """`--full` (side measurements, off by default) and `--dump-outputs DIR`
+    are accepted; --steps must name at least one timed step."""
+    r = _bench(["--help"])
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = _bench(["--gpus", "1", "--steps", "0", "--launch-check"])
+    assert r.returncode != 0 and "--steps" in r.stderr

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Durations of the isolated-batch chain bench.py replays last (after its
+"""Durations of the isolated-batch chain bench.py --full replays last (after its
 timed region), from a rocprofv3 --kernel-trace CSV: the rocprof side of the
 roofline's per-launch time (bench.py "isolated_batch_ms").
 

@@ -51,7 +51,7 @@ def main(src, dst, batches=1):
                 v = [x for x in v if x[0] == g]
             out.setdefault(k, {})[c + "_KB_per_launch"] = round(sum(y for _, y in v) / chains, 1)
             out[k]["calls_per_launch"] = round(len(v) / chains, 2)
-    doc = {"command": "rocprofv3 --pmc FETCH_SIZE (resp. WRITE_SIZE) -f csv -- python3 bench.py --no-cpu "
+    doc = {"command": "rocprofv3 --pmc FETCH_SIZE (resp. WRITE_SIZE) -f csv -- python3 bench.py --full --no-cpu "
                       "--inflight 1 --merge %d --steps %d --warmup 0 --api-batches 0 (tools/gpu_pmc.sh)" % (batches, batches),
            "note": "one counter group per pass; raw values in KB per launch.  bench.py counts FETCH_SIZE x 2 (the "
                    "gfx950 correction of MI355X_MICROARCH.md, calibrated for 16-B/lane streaming reads) + WRITE_SIZE; "

@@ -15,5 +15,5 @@ for x in SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64; do
   if grep -qx "$x" $O/sq_counters.txt; then C="$C $x"; fi
 done
 echo "counters: $C"
-timeout -s KILL 120 rocprofv3 --pmc $C -f csv -d $O/pmc -o run -- python3 $R/bench.py --no-cpu --steps 4 --inflight 1 > $O/pmc.log 2>&1
+timeout -s KILL 120 rocprofv3 --pmc $C -f csv -d $O/pmc -o run -- python3 $R/bench.py --full --no-cpu --steps 4 --inflight 1 > $O/pmc.log 2>&1
 echo "== done"

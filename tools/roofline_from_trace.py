@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Recompute bench.py's `roofline` from a rocprofv3 kernel trace of the same
-command (the reproducibility check of the bench line).
+"""Recompute `bench.py --full`'s `roofline` from a rocprofv3 kernel trace of
+the same command (the reproducibility check of the bench line).
 
-bench.py prices the dominant kernel of ONE device batch replayed alone
+bench.py --full prices the dominant kernel of ONE device batch replayed alone
 (tbg_replay_profile, after its timed region).  In the trace of that command
 the kernel's dispatches of the full device-batch grid that overlap NO other
 dispatch are those exclusive runs (the replay_profile pass, and the

@@ -36,7 +36,7 @@ def main(src, dst):
             "valu_busy": round(d["SQ_ACTIVE_INST_VALU"] / max(d["SQ_WAVE_CYCLES"], 1), 3),
         }
     doc = {"command": "rocprofv3 --pmc " + " ".join(sorted(next(iter(agg.values())).keys())) +
-                      " -f csv -- python3 bench.py --no-cpu --steps 4 --inflight 1 (tools/pmc_valu.sh)",
+                      " -f csv -- python3 bench.py --full --no-cpu --steps 4 --inflight 1 (tools/pmc_valu.sh)",
            "kernels": out}
     with open(dst, "w") as f:
         json.dump(doc, f, indent=1)
