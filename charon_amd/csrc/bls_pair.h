@@ -89,6 +89,23 @@ TBG_HD Jac<F> g2_psi_g(const Jac<F>& p) {
   return {f_mulc(f_conj(p.X), PSI_X), f_mulc(f_conj(p.Y), PSI_Y), f_reduce(f_conj(p.Z))};
 }
 
+// Fused level 0's signature side (bls_rlc.h, top; k_l0f_horner): one Horner
+// step 13 acc + q by 3 doublings + 2 additions (13 = 1101b) and the addition
+// of q, and the term psi^j(2 A + T) of dimension j.  The complete additions:
+// small multiples of one point (equal signatures) do meet the doubling case.
+template <class F>
+TBG_HD Jac<F> l0f_mul13_add(const Jac<F>& acc, const Jac<F>& q) {
+  Jac<F> t = jac_add_in<F, true>(jac_dbl_in(acc), acc);  // 3 acc
+  t = jac_add_in<F, true>(jac_dbl_in(jac_dbl_in(t)), acc);  // 13 acc
+  return jac_add_in<F, true>(t, q);
+}
+template <class F>
+TBG_HD Jac<F> l0f_term(const Jac<F>& A, const Jac<F>& T, int j) {
+  Jac<F> r = jac_add_in<F, true>(jac_dbl_in(A), T);
+  for (int k = 0; k < j; ++k) r = g2_psi_g(r);
+  return r;
+}
+
 // Jacobian addition without the P == Q branch: when it would be needed
 // (H == 0 with R == 0, a doubling) `exc` is set and the result is unusable;
 // the caller redoes the item on the reference path.  P == -Q and infinities

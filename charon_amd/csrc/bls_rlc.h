@@ -16,6 +16,39 @@
 // of {+-(q0 + q1), +-(q0 - q1)} per pair: 15 doublings + 31 additions in
 // uniform control flow.  (Unsigned 0/1 digits made the additions of the
 // four points lane-divergent: a wave executed all 64 of them, masked.)
+//
+// Fused level 0 (l0f_* below; k_sgb.hip, k_msm.hip).  While the batched
+// subgroup test runs, level 0 draws no scalar of its own: r_i is a fixed
+// public linear form of the partial's 18 secret subgroup digits c_0..c_17 in
+// {-6..6} (sgb_digits).  The digits are split over the four dimensions,
+// digits 0-4 -> j = 0, 5-9 -> j = 1, 10-13 -> j = 2, 14-17 -> j = 3:
+//   rho_j = sum_e 13^e c_(first_j + e),   a_j = 2 rho_j + 1   (always odd),
+//   r_i = a_0 + a_1 x + a_2 x^2 + a_3 x^3,
+//   |a_0|, |a_1| <= 371,293 < 2^19,   |a_2|, |a_3| <= 28,561 < 2^15,
+// each a_j in the signed-binary form above, u_j = (a_j + 2^n - 1) / 2 =
+// rho_j + 2^(n - 1) with n = 20 for j = 0, 1 and n = 16 for j = 2, 3: ten
+// 2-bit windows of the key table for the (pk, [x]pk) pair and eight for its
+// phi image, 18 doublings + 18 additions.  With Qbar_k = sum_i c_ik s_i (the
+// subgroup test's sums Q_k added over the groups) and T = sum_i s_i,
+//   S = sum_i r_i s_i = sum_j psi^j(2 A_j + T),  A_j = sum_e 13^e Qbar_(first_j + e):
+// no second pass over the signatures.  (psi is a homomorphism of the whole
+// curve, so this is sum_i sum_j a_ij psi^j(s_i) for any points; it equals
+// sum_i r_i s_i because the subgroup test has put every Q_k, hence with its
+// own bound every s_i, in G2, where psi = [x].)
+// Soundness.  Base-13 digits in {-6..6} represent distinct integers, so
+// distinct digit vectors give distinct (a_0..a_3); the differences of the
+// a_j are below 2^20 < |x| and 2^20 |x|^3 < r, so they give distinct r_i mod
+// r: r_i takes 13^18 near-uniform secret values (bias < 2^-17 per digit) and
+// a false accept at level 0 has probability <= 13^-18 < 2^-66, against 2^-64
+// for the 64-bit scalars.  Sharing the key between the two checks is sound:
+// a forged batch either holds a signature outside G2 -- then the subgroup
+// test fails its group with its own bound (k_sgb.hip), whatever level 0
+// does with the same digits, and a failed group voids the fused level 0 --
+// or holds only G2 points, and then the subgroup test's verdicts do not
+// depend on the digits at all (every combination of G2 points is in G2), so
+// they reveal nothing about them and the RLC bound holds for the digits as
+// for fresh ones.  sgb_seed is fresh OS entropy for every launch even under
+// a fixed rlc_seed, so a fixed rlc_seed does not fix level 0's scalars here.
 #pragma once
 #include "bls_h2c.h"
 
@@ -169,6 +202,43 @@ TBG_HD Jac<F> rlc_mul_key_w2(const Aff<F>* tab, const Fp& c, const uint32_t (&u)
   acc = jac_add_aff_in(acc, rlc_entry_w2(tab, rlc_win2(u[2], 7), rlc_win2(u[3], 7), true, c));
 #pragma unroll 1
   for (int i = 6; i >= 0; --i) {
+    acc = jac_dbl_in(jac_dbl_in(acc));
+    acc = jac_add_aff_in(acc, rlc_entry_w2(tab, rlc_win2(u[0], i), rlc_win2(u[1], i), false, c));
+    acc = jac_add_aff_in(acc, rlc_entry_w2(tab, rlc_win2(u[2], i), rlc_win2(u[3], i), true, c));
+  }
+  return acc;
+}
+
+// Fused level 0 (see top): the four digits u_j = rho_j + 2^(n_j - 1) of
+// r_i from the partial's subgroup digits, and rho_j / a_j themselves.
+TBG_HD int l0f_first(int j) { return j < 2 ? 5 * j : 10 + 4 * (j - 2); }  // j = 4: 18
+TBG_HD int l0f_bits(int j) { return j < 2 ? 20 : 16; }
+TBG_HD void l0f_rho(const int32_t (&c)[18], int32_t (&rho)[4]) {
+  for (int j = 0; j < 4; ++j) {
+    int32_t v = 0;
+    for (int e = l0f_first(j + 1) - 1; e >= l0f_first(j); --e) v = 13 * v + c[e];
+    rho[j] = v;
+  }
+}
+TBG_HD void l0f_scalar(const int32_t (&c)[18], int32_t (&a)[4]) {
+  int32_t rho[4];
+  l0f_rho(c, rho);
+  for (int j = 0; j < 4; ++j) a[j] = 2 * rho[j] + 1;
+}
+TBG_HD void l0f_digits(const int32_t (&c)[18], uint32_t (&u)[4]) {
+  int32_t rho[4];
+  l0f_rho(c, rho);
+  for (int j = 0; j < 4; ++j) u[j] = (uint32_t)(rho[j] + (1 << (l0f_bits(j) - 1)));
+}
+// [r_i] pk from the key's window table and the fused digits: windows 9 and 8
+// of the (pk, [x]pk) pair alone, then the eight common windows.
+template <class F>
+TBG_HD Jac<F> rlc_mul_key_l0f(const Aff<F>* tab, const Fp& c, const uint32_t (&u)[4]) {
+  Jac<F> acc = jac_from_aff(rlc_entry_w2(tab, rlc_win2(u[0], 9), rlc_win2(u[1], 9), false, c));
+  acc = jac_dbl_in(jac_dbl_in(acc));
+  acc = jac_add_aff_in(acc, rlc_entry_w2(tab, rlc_win2(u[0], 8), rlc_win2(u[1], 8), false, c));
+#pragma unroll 1
+  for (int i = 7; i >= 0; --i) {
     acc = jac_dbl_in(jac_dbl_in(acc));
     acc = jac_add_aff_in(acc, rlc_entry_w2(tab, rlc_win2(u[0], i), rlc_win2(u[1], i), false, c));
     acc = jac_add_aff_in(acc, rlc_entry_w2(tab, rlc_win2(u[2], i), rlc_win2(u[3], i), true, c));

@@ -55,7 +55,7 @@ __global__ void TBG_LAUNCH_N(TBG_DECODE_WAVES) k_decode_sigs(DevBatch B) {
   // bucket sizes (a runtime memset kernel queued behind other streams' waves
   // held each chain for ~2 ms in the pipelined bench)
   if (i < CNT_WORDS) B.counters[i] = 0;
-  if (B.rlc_batch && i <= MSM_BUCKETS) B.msm_off[i] = 0;
+  if (B.rlc_batch && !l0_fused(B) && i <= MSM_BUCKETS) B.msm_off[i] = 0;  // (the fused level 0 has no buckets)
   if (i >= B.n_partials) return;
   // decoded from the input bytes straight into the output slot: x and the
   // root's input wait there while the exponentiations run (the root inline:
@@ -98,7 +98,7 @@ void launch_decode_pubkeys(const uint8_t* pk48, uint32_t n, G1A* out, G1A* out_x
 void launch_decode_sigs(const DevBatch& B, hipStream_t st) {
   // at least enough lanes to zero the counters (and level 0's bucket sizes)
   uint32_t lanes = B.n_partials > CNT_WORDS ? B.n_partials : CNT_WORDS;
-  if (B.rlc_batch && lanes < MSM_BUCKETS + 1) lanes = MSM_BUCKETS + 1;
+  if (B.rlc_batch && !l0_fused(B) && lanes < MSM_BUCKETS + 1) lanes = MSM_BUCKETS + 1;
   TBG_KLAUNCH(k_decode_sigs, grid_for(lanes), dim3(kBlock), st, B);
   launch_subgroup_batch(B, st);
   if (B.n_partials) TBG_KLAUNCH(k_subgroup_sigs, grid_for(2 * B.n_partials), dim3(kBlock), st, B);

@@ -59,6 +59,7 @@ __device__ __forceinline__ bool gm_member(const DevBatch& B, uint32_t i) {
 // others [r_i] pk_i from the key's window table.
 __global__ void TBG_LAUNCH k_rlc_g1(DevBatch B, const G1A* tab, const G1A* pk_aff, const int32_t* pk_status,
                                    uint32_t n_pk) {
+  if (B.counters[CNT_L0_OK]) return;  // (after a fused level 0: it accepted the batch)
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B.n_partials || B.partial_status[i] != TBG_PS_NOT_VERIFIED) return;
   const uint32_t pid = B.pubkey_ids[i];

@@ -181,7 +181,10 @@ __global__ void TBG_LAUNCH_N(TBG_HEX_WAVES) k_miller_hex(DevBatch B) {
   const uint32_t np_q = MODE == MILLER_GROUP_S ? 0u : n_groups * nch;
   const uint32_t qd = hex_slot(t);
   if (qd == 0xFFFFFFFFu || qd >= np_q + (MODE == MILLER_L0 ? 1u : n_groups)) return;
-  if (MODE == MILLER_GROUP_S && B.counters[CNT_L0_OK]) return;  // level 0 accepted the batch
+  // level 0 accepted the batch (MILLER_GROUPS: enqueued blind after a fused level 0)
+  if (MODE != MILLER_L0 && B.counters[CNT_L0_OK]) return;
+  // a void fused level 0 keeps nothing: its P chunks would be formed again with the classic scalars
+  if (MODE == MILLER_L0 && l0_fused(B) && B.counters[CNT_L0_BAD]) return;
   const bool s_quad = qd >= np_q;
   const uint32_t* ls = nullptr;
   uint32_t* dst;

@@ -18,6 +18,10 @@
 //   k_msm_bucket_part  one lane PAIR per quarter of a bucket: its sum
 //   k_msm_bucket     one lane PAIR per bucket: the quarters' sum times (2j + 1)
 //   k_msm_tree, k_msm_tree_final  the sum of the scaled buckets (LDS trees), S affine
+// While the batched subgroup test runs for the launch (l0_fused, tbls_launch.h)
+// the k_msm_* kernels do not run: r_i is a form of the partial's subgroup
+// digits (bls_rlc.h, top) and S comes from that test's sums -- see "fused
+// level 0" below (k_l0f_reduce, k_l0f_fold, k_l0f_horner).
 #define TBG_ADD_DBL_INLINE 1
 #ifndef TBG_SCHED_FENCE
 #define TBG_SCHED_FENCE 1  // products in program order: fits the pair kernels in 256 VGPRs (bls_field.h)
@@ -72,8 +76,16 @@ __global__ void TBG_LAUNCH k_rlc_g1_l0(DevBatch B, const G1A* tab, const int32_t
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B.n_partials || B.partial_status[i] != TBG_PS_NOT_VERIFIED) return;
   const uint32_t pid = B.pubkey_ids[i];
+  const bool fused = l0_fused(B);
   if (pid >= n_pk || pk_status[pid] != DEC_OK) {
     B.partial_status[i] = TBG_PS_ERR_PUBKEY;
+    if (fused) B.counters[CNT_L0_BAD] = 1;  // the fused S holds this partial: level 0 is void
+    return;
+  }
+  if (fused) {  // r_i from the subgroup digits (k_sgb_sort stored its u_j): nothing kept for an MSM
+    const uint4 v = *(const uint4*)(B.l0f_u + 4ull * i);
+    const uint32_t uf[4] = {v.x, v.y, v.z, v.w};
+    B.part_p[i] = rlc_mul_key_l0f(tab + (size_t)PK_TAB * pid, fp_from_const(G1_BETA), uf);
     return;
   }
   const uint64_t r = rlc_scalar(B.rlc_seed, i);
@@ -287,6 +299,76 @@ __global__ void __launch_bounds__(MSM_TREE_WG) k_msm_tree_final(DevBatch B) {
   px_store(*B.batch_pt, Aff<Fp2x>{f_mul(acc.X, zi2), f_mul(acc.Y, f_mul(zi2, zi))});
 }
 
+// ------------------------------------------------------- fused level 0
+// S from the batched subgroup test's sums (bls_rlc.h, top): the 18 columns
+// Qbar_k = sum over the groups of Q_k (k_sgb_combine left Q_k in the first
+// slot of combination k's buckets, k_sgb_test proved it in G2) and the
+// column T (k_sgb_bucket's slice sums), then
+//   S = sum_j psi^j(2 A_j + T),  A_j = sum_e 13^e Qbar_(first_j + e).
+//   k_l0f_reduce  one workgroup per L0F_CHUNK points of a column: their sum
+//   k_l0f_fold    one workgroup per column: the sum of its chunk sums
+//   k_l0f_horner  one lane pair per j: A_j by Horner steps, psi^j(2 A_j + T); S affine
+// A failed subgroup group voids level 0 (its Q_k are not in G2 and its
+// members are about to be tested alone: k_sgb.hip sets the flag with
+// sgb_bad), as does a key mark made after the sort (k_rlc_g1_l0) and S = 0.  Every addition takes the complete formulas:
+// small multiples of one point (equal signatures) do meet the doubling case.
+__global__ void __launch_bounds__(2 * L0F_PAIRS) k_l0f_reduce(DevBatch B, uint32_t n_sg, uint32_t wq, uint32_t n_t) {
+  __shared__ Jac<Fp2x> lds[2 * L0F_PAIRS];
+  if (B.counters[CNT_L0_BAD]) return;  // (grid-uniform: set before this kernel starts)
+  const uint32_t pr = threadIdx.x >> 1, b = blockIdx.x;
+  const bool qcol = b < SGB_K * wq;
+  const uint32_t col = qcol ? b / wq : SGB_K, chunk = qcol ? b % wq : b - SGB_K * wq;
+  const uint32_t count = qcol ? n_sg : n_sg * n_t;
+  const uint32_t a0 = chunk * L0F_CHUNK + pr * L0F_PER, a1 = min(a0 + L0F_PER, count);
+  Jac<Fp2x> acc = jac_inf<Fp2x>();
+#pragma unroll 1
+  for (uint32_t a = a0; a < a1; ++a) {  // (pair-uniform)
+    if (qcol) {
+      acc = jac_add_in<Fp2x, true>(acc, px_load(B.sgb_part[((size_t)SGB_BUCKETS * a + (size_t)SGB_V * col) * B.sgb_split]));
+    } else {
+      acc = jac_add_in<Fp2x, true>(acc, px_load(B.sgb_t[a]));
+    }
+  }
+  acc = pair_tree_sum<L0F_PAIRS>(acc, lds);
+  if (pr == 0) px_store(B.l0f_sum[b], acc);
+}
+
+__global__ void __launch_bounds__(2 * L0F_PAIRS) k_l0f_fold(DevBatch B, uint32_t wq, uint32_t wt) {
+  TBG_URGENT();
+  __shared__ Jac<Fp2x> lds[2 * L0F_PAIRS];
+  if (B.counters[CNT_L0_BAD]) return;  // (grid-uniform)
+  const uint32_t pr = threadIdx.x >> 1, col = blockIdx.x;
+  const uint32_t first = col < SGB_K ? col * wq : SGB_K * wq, count = col < SGB_K ? wq : wt;
+  Jac<Fp2x> acc = jac_inf<Fp2x>();
+#pragma unroll 1
+  for (uint32_t a = pr; a < count; a += L0F_PAIRS) acc = jac_add_in<Fp2x, true>(acc, px_load(B.l0f_sum[first + a]));
+  acc = pair_tree_sum<L0F_PAIRS>(acc, lds);
+  if (pr == 0) px_store(B.l0f_sum[SGB_K * wq + wt + col], acc);
+}
+
+constexpr uint32_t L0F_HORNER_THREADS = 8;  // four lane pairs, one per j
+__global__ void __launch_bounds__(64) k_l0f_horner(DevBatch B, uint32_t base) {
+  TBG_URGENT();
+  __shared__ Jac<Fp2x> lds[L0F_HORNER_THREADS];
+  if (B.counters[CNT_L0_BAD]) return;
+  const int j = (int)(threadIdx.x >> 1);
+  const G2J* tot = B.l0f_sum + base;  // the column totals
+  const int e0 = l0f_first(j), e1 = l0f_first(j + 1);
+  Jac<Fp2x> acc = px_load(tot[e1 - 1]);
+#pragma unroll 1
+  for (int e = e1 - 2; e >= e0; --e) acc = l0f_mul13_add(acc, px_load(tot[e]));  // (pair-uniform trip counts)
+  acc = l0f_term(acc, px_load(tot[SGB_K]), j);
+  acc = pair_tree_sum<L0F_HORNER_THREADS / 2>(acc, lds);
+  if (j != 0) return;
+  if (jac_is_inf(acc)) {
+    if (pair_par() == 0) B.counters[CNT_L0_BAD] = 1;  // S = 0: no lines; the group levels decide
+    return;
+  }
+  const Fp2x zi = f_inv(acc.Z);
+  const Fp2x zi2 = f_sqr(zi);
+  px_store(*B.batch_pt, Aff<Fp2x>{f_mul(acc.X, zi2), f_mul(acc.Y, f_mul(zi2, zi))});
+}
+
 void launch_pubkey_tables(const G1A* pk, const G1A* xpk, const int32_t* status, uint32_t n, G1A* tab, hipStream_t st) {
   if (n) TBG_KLAUNCH(k_pubkey_tables, dim3((n + BINV_BLOCK - 1) / BINV_BLOCK), dim3(BINV_BLOCK), st, pk, xpk, status, n,
                      tab);
@@ -307,6 +389,15 @@ void launch_l0_msm(const DevBatch& B, hipStream_t st) {
   TBG_KLAUNCH(k_msm_bucket, grid_for(2 * MSM_BUCKETS), dim3(kBlock), st, B);
   TBG_KLAUNCH(k_msm_tree, dim3(MSM_TREE_WG), dim3(2 * MSM_TREE_PAIRS), st, B);
   TBG_KLAUNCH(k_msm_tree_final, dim3(1), dim3(MSM_TREE_WG), st, B);
+}
+
+// Fused level 0's signature side: S from the subgroup test's sums.
+void launch_l0_fused_s(const DevBatch& B, hipStream_t st) {
+  const uint32_t n_sg = sgb_groups(B.n_partials, B.sgb_m), n_t = sgb_t_slices(B.sgb_m);
+  const uint32_t wq = l0f_q_chunks(n_sg), wt = l0f_t_chunks(n_sg, B.sgb_m);
+  TBG_KLAUNCH(k_l0f_reduce, dim3(SGB_K * wq + wt), dim3(2 * L0F_PAIRS), st, B, n_sg, wq, n_t);
+  TBG_KLAUNCH(k_l0f_fold, dim3(L0F_COLS), dim3(2 * L0F_PAIRS), st, B, wq, wt);
+  TBG_KLAUNCH(k_l0f_horner, dim3(1), dim3(L0F_HORNER_THREADS), st, B, SGB_K * wq + wt);
 }
 
 }  // namespace tbg

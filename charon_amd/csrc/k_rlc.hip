@@ -80,6 +80,8 @@ __global__ void __launch_bounds__(BINV_BLOCK) k_rlc_duty_sum(DevBatch B) {
   constexpr int phase = PHASE;
   const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = d < B.n_duties;
+  // DSUM_P after a fused level 0 (launch_rlc_check): nothing to redo after a pass (grid-uniform)
+  if (phase == DSUM_P && B.counters[CNT_L0_OK]) return;
   if (phase == DSUM_FALLBACK_S) {  // (no inversion: no workgroup-wide step)
     if (!in || B.counters[CNT_L0_OK] || B.dv_state[d] != RLC_COMBINED) return;
 #if TBG_GMSM
@@ -901,7 +903,9 @@ void launch_rlc_prepare(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff
   if (B.rlc_batch) {  // level 0: G1 products, P_d, the signature MSM and S's lines
     launch_l0_keys(B, pk_tab, pk_status, n_pk, st);
     if (after_keys) after_keys(B, st);
-    launch_l0_msm(B, st);
+    // S: from the subgroup test's sums while the batched test runs, else the bucket MSM
+    if (l0_fused(B)) launch_l0_fused_s(B, st);
+    else launch_l0_msm(B, st);
     TBG_KLAUNCH(k_rlc_duty_sum<DSUM_L0_P>, duty_grid(B), dim3(BINV_BLOCK), st, B);
     launch_l0_lines(B, st);
     return;
@@ -920,9 +924,10 @@ void launch_rlc_prepare(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff
   launch_lines_fold(B, FOLD_GROUPS, n_groups, st);
 }
 
-void launch_rlc_check(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff, const int32_t* pk_status, uint32_t n_pk,
-                      hipStream_t st) {
-  if (!B.n_duties) return;
+void launch_rlc_check(const DevBatch& B0, const G1A* pk_aff, const G1A* xpk_aff, const G1A* pk_tab,
+                      const int32_t* pk_status, uint32_t n_pk, hipStream_t st) {
+  if (!B0.n_duties) return;
+  DevBatch B = B0;
   if (B.rlc_group != 0) {
     uint32_t n_groups = (B.n_duties + B.rlc_group - 1) / B.rlc_group;
     uint32_t nch = (B.rlc_group + B.rlc_chunk - 1) / B.rlc_chunk;
@@ -944,6 +949,19 @@ void launch_rlc_check(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff, 
       TBG_KLAUNCH(k_l0_after, grid_for(n_groups), dim3(kBlock), st, B);
       // level 0 failed: the group levels' signature side (these kernels
       // return at once after a pass)
+      if (l0_fused(B)) {
+        // The fused scalars have another format than the group levels' (no
+        // 16-bit digits for the group MSM and the exponent tests), so a void
+        // or failed fused level 0 leaves nothing to reuse: the launch goes on
+        // as one with level 0 off -- the classic scalars (rlc_scalar, group
+        // leads), G1 products, P_d and the P chunks formed again.
+        B.rlc_batch = 0;
+        launch_rlc_g1(B, pk_tab, pk_aff, pk_status, n_pk, st);
+        TBG_KLAUNCH(k_rlc_duty_sum<DSUM_P>, duty_grid(B), dim3(BINV_BLOCK), st, B);
+        launch_gm_group_s(B, st);
+        launch_lines_fold(B, FOLD_GROUPS, n_groups, st);
+        launch_groups_miller_hex(B, st);
+      } else {
 #if TBG_GMSM
       launch_gm_group_s(B, st);  // (G1 products, P_d and r_i: level 0's)
 #else
@@ -953,6 +971,7 @@ void launch_rlc_check(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff, 
 #endif
       launch_lines_fold(B, FOLD_GROUPS, n_groups, st);
       launch_group_s_miller_hex(B, st);
+      }
     } else {
       launch_groups_miller_hex(B, st);
     }

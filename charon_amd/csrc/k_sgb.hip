@@ -24,6 +24,9 @@
 //   k_sgb_combine one lane PAIR per (group, combination): Q_k from its buckets
 //   k_sgb_test    one lane PAIR per (group, combination): psi(Q_k) == [x] Q_k
 // then k_subgroup_sigs tests the members of failed groups one by one.
+// With the fused level 0 (bls_rlc.h, top) the same sums serve level 0's
+// S = sum r_i s_i: k_sgb_sort also stores the digits of r_i, k_sgb_bucket also
+// adds the group's unweighted sum T, and a failed group voids level 0.
 #define TBG_ADD_DBL_INLINE 1
 #ifndef TBG_SCHED_FENCE
 #define TBG_SCHED_FENCE 1  // products in program order: fits the pair kernels in 256 VGPRs (bls_field.h)
@@ -48,11 +51,17 @@ __global__ void __launch_bounds__(kSgbSortBlock) k_sgb_sort(DevBatch B) {
   const uint32_t n = min(m, B.n_partials - i0);
   for (uint32_t b = t; b < SGB_BUCKETS; b += kSgbSortBlock) cnt[b] = 0;
   if (t == 0) B.sgb_bad[g] = 0;
+  const bool fused = l0_fused(B);
   __syncthreads();
   for (uint32_t li = t; li < n; li += kSgbSortBlock) {
     const bool ok = B.partial_status[i0 + li] == TBG_PS_NOT_VERIFIED;
     int32_t c[SGB_K];
     sgb_digits(B.sgb_seed, i0 + li, c);
+    if (fused) {  // level 0's scalar of the partial is a form of these digits (bls_rlc.h; k_rlc_g1_l0 reads it)
+      uint32_t u[4];
+      l0f_digits(c, u);
+      *(uint4*)(B.l0f_u + 4ull * (i0 + li)) = make_uint4(u[0], u[1], u[2], u[3]);
+    }
 #pragma unroll
     for (uint32_t k = 0; k < SGB_K; ++k) {
       const int32_t d = ok ? c[k] : 0;
@@ -88,11 +97,29 @@ __global__ void __launch_bounds__(kSgbSortBlock) k_sgb_sort(DevBatch B) {
   }
 }
 
-// one lane pair per (group, bucket, slice)
-__global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_bucket(DevBatch B, uint32_t n_sg) {
+// one lane pair per (group, bucket, slice); with the fused level 0 the pairs
+// after them, one per (group, SGB_T_PER consecutive members), add the group's
+// unweighted sum T: one more bucket with coefficient +1 whose members are the
+// candidates at sort time (nothing changes a status between the two kernels)
+__global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_bucket(DevBatch B, uint32_t n_sg, uint32_t n_t) {
   const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;  // both lanes of a pair take the same branches
   const uint32_t S = B.sgb_split, m = B.sgb_m;
-  if (w >= n_sg * SGB_BUCKETS * S) return;
+  if (w >= n_sg * SGB_BUCKETS * S) {
+    const uint32_t wt = w - n_sg * SGB_BUCKETS * S;
+    if (wt >= n_sg * n_t) return;
+    const uint32_t i0 = (wt / n_t) * m + (wt % n_t) * SGB_T_PER;
+    const uint32_t i1 = min(min(i0 + SGB_T_PER, (wt / n_t + 1) * m), B.n_partials);
+    Jac<Fp2x> acc = jac_inf<Fp2x>();
+#pragma unroll 1
+    for (uint32_t i = i0; i < i1; ++i) {  // (i0 >= n_partials in the last group's tail: an empty slice)
+      if (B.partial_status[i] != TBG_PS_NOT_VERIFIED) continue;
+      Aff<Fp2x> p = px_load(B.sig_aff[i]);
+      p.y = f_reduce(p.y);
+      acc = jac_add_aff_in(acc, p);
+    }
+    px_store(B.sgb_t[wt], acc);
+    return;
+  }
   const uint32_t g = w / (SGB_BUCKETS * S), b = (w / S) % SGB_BUCKETS, sl = w % S;
   const uint32_t* goff = B.sgb_off + (size_t)(SGB_BUCKETS + 1) * g;
   const uint32_t o0 = goff[b], n = goff[b + 1] - o0;
@@ -109,6 +136,13 @@ __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_bucket(DevBatch B, uint32_t n
     acc = jac_add_aff_in(acc, p);
   }
   px_store(B.sgb_part[w], acc);
+}
+
+// A failed group: its members are tested alone, and the fused level 0, whose
+// S is built from the groups' sums (k_msm.hip), is void for the launch.
+__device__ __forceinline__ void sgb_fail(const DevBatch& B, uint32_t g) {
+  B.sgb_bad[g] = 1u;
+  if (l0_fused(B)) B.counters[CNT_L0_BAD] = 1u;
 }
 
 // one lane pair per (group, bucket): the bucket's SGB_SPLIT slice sums into
@@ -128,7 +162,7 @@ __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_fold(DevBatch B, uint32_t n_s
 #pragma unroll 1
   for (uint32_t sl = 1; sl < S; ++sl) acc = jac_add_x(acc, px_load(part[sl]), exc);
   if (pair_all(!exc)) px_store(part[0], acc);
-  else if (pair_par() == 0) B.sgb_bad[w / SGB_BUCKETS] = 1u;
+  else if (pair_par() == 0) sgb_fail(B, w / SGB_BUCKETS);
 }
 
 // one lane pair per (group, combination): Q_k = sum_v v B_v by running sums
@@ -147,7 +181,7 @@ __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_combine(DevBatch B, uint32_t 
     q = jac_add_x(q, run, exc);
   }
   if (pair_all(!exc)) px_store(part[0], q);
-  else if (pair_par() == 0) B.sgb_bad[g] = 1u;
+  else if (pair_par() == 0) sgb_fail(B, g);
 }
 
 // one lane pair per (group, combination): psi(Q) == [x] Q; a failure (or the
@@ -182,7 +216,7 @@ __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_test(DevBatch B, uint32_t n_s
            f_eq(f_mul(f_mul(ps.Y, m.Z), z2), f_reduce(f_neg(f_mul(f_mul(m.Y, ps.Z), z1))));
     }
   }
-  if (!ok && pair_par() == 0) B.sgb_bad[g] = 1u;
+  if (!ok && pair_par() == 0) sgb_fail(B, g);
 }
 
 void launch_subgroup_batch(const DevBatch& B, hipStream_t st) {
@@ -190,7 +224,8 @@ void launch_subgroup_batch(const DevBatch& B, hipStream_t st) {
   const uint32_t n_sg = sgb_groups(B.n_partials, B.sgb_m);
   if (!n_sg) return;
   TBG_KLAUNCH(k_sgb_sort, dim3(n_sg), dim3(kSgbSortBlock), st, B);
-  TBG_KLAUNCH(k_sgb_bucket, grid_for(2 * n_sg * SGB_BUCKETS * B.sgb_split), dim3(kBlock), st, B, n_sg);
+  const uint32_t n_t = l0_fused(B) ? sgb_t_slices(B.sgb_m) : 0u;  // the slices of T per group
+  TBG_KLAUNCH(k_sgb_bucket, grid_for(2 * n_sg * (SGB_BUCKETS * B.sgb_split + n_t)), dim3(kBlock), st, B, n_sg, n_t);
   if (B.sgb_split > 1) TBG_KLAUNCH(k_sgb_fold, grid_for(2 * n_sg * SGB_BUCKETS), dim3(kBlock), st, B, n_sg);
   TBG_KLAUNCH(k_sgb_combine, grid_for(2 * n_sg * SGB_K), dim3(kBlock), st, B, n_sg);
   TBG_KLAUNCH(k_sgb_test, grid_for(2 * n_sg * SGB_K), dim3(kBlock), st, B, n_sg);

@@ -506,7 +506,8 @@ static int launch_chain(tbg_ctx* c, const Slot& sl, const DevBatch& B, hipEvent_
   if (stage >= 0 && stage != 2) return TBG_OK;
   HIP_TRY(hipStreamWaitEvent(st, ev[5], 0));
   HIP_TRY(hipEventRecord(ev[6], st));
-  if (verify) launch_rlc_check(B, pk, (const G1A*)c->d_xpk, (const int32_t*)c->d_pk_status, c->n_pk, st);
+  if (verify) launch_rlc_check(B, pk, (const G1A*)c->d_xpk, (const G1A*)c->d_pktab, (const int32_t*)c->d_pk_status,
+                                 c->n_pk, st);
   HIP_TRY(hipEventRecord(ev[7], st));
   if (B.op != TBG_OP_VERIFY) launch_lagrange(B, st);
   HIP_TRY(hipEventRecord(ev[8], st));
@@ -763,13 +764,6 @@ int tbg_submit_group(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches,
   size_t w_gidf = sec(G > 1 ? 4ull * 3 * 4 * NL * ng * (nch + 1) : 0);
   size_t w_idl = sec(G > 1 ? 4ull * nd : 0);
   size_t w_idp = sec(G > 1 ? sizeof(G1A) * (size_t)nd : 0);
-  size_t w_mr = sec(l0 ? 8ull * np : 0);
-  size_t w_moff = sec(l0 ? 4ull * (MSM_BUCKETS + 1) : 0);
-  size_t w_mcur = sec(l0 ? 4ull * MSM_BUCKETS : 0);
-  size_t w_ment = sec(l0 ? 16ull * np : 0);
-  size_t w_mbkt = sec(l0 ? sizeof(G2J) * (size_t)MSM_BUCKETS : 0);
-  size_t w_mpart = sec(l0 ? sizeof(G2J) * (size_t)MSM_BUCKETS * MSM_SPLIT : 0);
-  size_t w_msum = sec(l0 ? sizeof(G2J) * (size_t)MSM_SUM_ENTRIES : 0);
   size_t w_bpt = sec(l0 ? sizeof(G2A) : 0);
   size_t w_blines = sec(l0 ? 4ull * LINES_WORDS : 0);
   size_t w_bf = sec(l0 ? 4ull * 3 * 4 * NL : 0);
@@ -795,6 +789,22 @@ int tbg_submit_group(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches,
   size_t w_sgent = sec(4ull * sgb_m * SGB_K * n_sg);
   size_t w_sgpart = sec(sizeof(G2J) * SGB_BUCKETS * sgb_split * n_sg);
   size_t w_sgbad = sec(4ull * n_sg);
+  // Level 0's signature side: with the batched test on, S comes from the
+  // test's sums (l0_fused, tbls_launch.h; a replayed prefix of the launch
+  // keeps both flags, so it takes the same path) and the bucket MSM's
+  // arrays are not needed; otherwise the bucket MSM of k_msm.hip.
+  const bool fused = l0 && sgb && TBG_PK_W2;
+  const bool msm = l0 && !fused;
+  size_t w_mr = sec(msm ? 8ull * np : 0);
+  size_t w_moff = sec(msm ? 4ull * (MSM_BUCKETS + 1) : 0);
+  size_t w_mcur = sec(msm ? 4ull * MSM_BUCKETS : 0);
+  size_t w_ment = sec(msm ? 16ull * np : 0);
+  size_t w_mbkt = sec(msm ? sizeof(G2J) * (size_t)MSM_BUCKETS : 0);
+  size_t w_mpart = sec(msm ? sizeof(G2J) * (size_t)MSM_BUCKETS * MSM_SPLIT : 0);
+  size_t w_msum = sec(msm ? sizeof(G2J) * (size_t)MSM_SUM_ENTRIES : 0);
+  size_t w_sgt = sec(fused ? sizeof(G2J) * sgb_t_slices(sgb_m) * n_sg : 0);
+  size_t w_l0fsum = sec(fused ? sizeof(G2J) * (size_t)l0f_sum_entries((uint32_t)n_sg, sgb_m) : 0);
+  size_t w_l0fu = sec(fused ? 16ull * np : 0);
   size_t w_aacc = sec(op != TBG_OP_VERIFY ? sizeof(G2J) * (size_t)nd : 0);
   size_t w_alist = sec(op != TBG_OP_VERIFY ? 4ull * nd : 0);
   size_t w_out = o;  // outputs are contiguous so one D2H copy brings them back
@@ -1010,6 +1020,9 @@ int tbg_submit_group(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches,
   B.sgb_ent = (uint32_t*)(dw + w_sgent);
   B.sgb_part = (G2J*)(dw + w_sgpart);
   B.sgb_bad = (uint32_t*)(dw + w_sgbad);
+  B.sgb_t = (G2J*)(dw + w_sgt);
+  B.l0f_sum = (G2J*)(dw + w_l0fsum);
+  B.l0f_u = (uint32_t*)(dw + w_l0fu);
   B.agg_acc = (G2J*)(dw + w_aacc);
   B.agg_list = (uint32_t*)(dw + w_alist);
 
@@ -1706,7 +1719,7 @@ int tbg_fast_aggregate_verify(tbg_ctx* c, const uint32_t* pubkey_ids, const uint
   tbg::launch_hash_msgs(B, st);
   tbg::launch_h_lines(B, st);
   tbg::launch_rlc_prepare(B, t_pk, t_xpk, nullptr, t_pkst, n, st);
-  tbg::launch_rlc_check(B, t_pk, t_xpk, t_pkst, n, st);
+  tbg::launch_rlc_check(B, t_pk, t_xpk, nullptr, t_pkst, n, st);  // (per-item schedule: no key table)
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(status, B.partial_status, 4ull * n, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));

@@ -152,7 +152,9 @@ struct DevBatch {
   // level 0 (k_msm.hip, k_rlc.hip): the whole device batch as ONE RLC check,
   //   prod_d e(P_d, H(m_d)) * e(-g1, S) == 1,  S = sum_i r_i s_i,
   // S as a bucket MSM over the signatures and their psi images (no per-partial
-  // G2 scalar multiplication); a failure falls through to the group levels
+  // G2 scalar multiplication) -- or, while the batched subgroup test runs, from
+  // that test's sums (l0_fused below; the msm_* arrays are then not allocated);
+  // a failure falls through to the group levels
   uint32_t rlc_batch;     // 1: level 0 runs first (every candidate's r_i random, no group lead)
   uint64_t* msm_r;        // [n_partials] r_i of the candidates
   uint32_t* msm_off;      // [MSM_BUCKETS + 1] bucket sizes, then their offsets
@@ -191,6 +193,11 @@ struct DevBatch {
   uint32_t* sgb_ent;      // [n_sg][sgb_m * SGB_K] entries: member << 1 | negative
   G2J* sgb_part;          // [n_sg][SGB_BUCKETS][sgb_split] bucket slice sums
   uint32_t* sgb_bad;      // [n_sg] 1: some combination is outside G2 (members tested alone)
+  // fused level 0 (l0_fused below): S from the subgroup test's sums
+  G2J* sgb_t;             // [n_sg][sgb_t_slices(sgb_m)] slice sums of the group's unweighted candidates
+  G2J* l0f_sum;           // [l0f_sum_entries] chunk sums of the Q_k columns and of T (k_l0f_reduce), then
+                          // the L0F_COLS column totals (k_l0f_fold)
+  uint32_t* l0f_u;        // [n_partials][4] the digits u_j of the fused r_i (k_sgb_sort -> k_rlc_g1_l0)
   // recombination (k_aggregate.hip)
   G2J* agg_acc;           // [n_duties] integer-coefficient sums awaiting [1/D] (listed duties only)
   uint32_t* agg_list;     // [n_duties] duties whose Lagrange denominator D > 1
@@ -242,6 +249,24 @@ TBG_HD uint32_t sgb_groups(uint32_t n_partials, uint32_t m) { return (n_partials
 TBG_HD uint32_t sgb_split_for(uint32_t m) {
   const uint32_t s = SGB_SPLIT * m / SGB_M;
   return s ? s : 1u;
+}
+// Fused level 0 (bls_rlc.h, k_msm.hip): while the batched subgroup test runs,
+// r_i is a fixed linear form of the partial's 18 subgroup digits, so S is a
+// fixed linear form of the test's sums Q_k (summed over the groups) and of the
+// unweighted sum T of the candidates -- no bucket MSM.  The host and every
+// kernel decide the path from the launch's own fields.
+TBG_HD bool l0_fused(const DevBatch& B) {
+  return TBG_PK_W2 && B.rlc_batch && B.rlc_group && B.sgb && B.n_partials;  // (the key products use the window table)
+}
+constexpr uint32_t SGB_T_PER = 32;  // candidates per slice of T (no longer a chain than a bucket slice's ~40)
+TBG_HD uint32_t sgb_t_slices(uint32_t m) { return m / SGB_T_PER; }  // (m: a power of two >= SGB_M_MIN = 64)
+constexpr uint32_t L0F_COLS = SGB_K + 1;        // the 18 sums over the groups of Q_k, then T
+constexpr uint32_t L0F_PAIRS = 128, L0F_PER = 4;  // k_l0f_reduce: lane pairs per workgroup, points per pair
+constexpr uint32_t L0F_CHUNK = L0F_PAIRS * L0F_PER;
+TBG_HD uint32_t l0f_q_chunks(uint32_t n_sg) { return (n_sg + L0F_CHUNK - 1) / L0F_CHUNK; }
+TBG_HD uint32_t l0f_t_chunks(uint32_t n_sg, uint32_t m) { return (n_sg * sgb_t_slices(m) + L0F_CHUNK - 1) / L0F_CHUNK; }
+TBG_HD uint32_t l0f_sum_entries(uint32_t n_sg, uint32_t m) {
+  return SGB_K * l0f_q_chunks(n_sg) + l0f_t_chunks(n_sg, m) + L0F_COLS;
 }
 // Level-0 product tree over the groups' P-chunk products.  Each pass is a
 // chain of F - 1 Fp12 products on one lane group (~24 us each at one wave per
@@ -359,13 +384,16 @@ void launch_h_lines(const DevBatch& B, hipStream_t st);
 void launch_rlc_prepare(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff, const G1A* pk_tab,
                         const int32_t* pk_status, uint32_t n_pk, hipStream_t st,
                         void (*after_keys)(const DevBatch&, hipStream_t) = nullptr);
-void launch_rlc_check(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff, const int32_t* pk_status, uint32_t n_pk,
-                      hipStream_t st);
+// pk_tab: for the group levels' G1 products after a void or failed fused level 0
+void launch_rlc_check(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff, const G1A* pk_tab,
+                      const int32_t* pk_status, uint32_t n_pk, hipStream_t st);
 void launch_lines_fold(const DevBatch& B, int kind, uint32_t max_entries, hipStream_t st);
 // level 0 (k_msm.hip)
 void launch_pubkey_tables(const G1A* pk, const G1A* xpk, const int32_t* status, uint32_t n, G1A* tab, hipStream_t st);
 void launch_l0_keys(const DevBatch& B, const G1A* pk_tab, const int32_t* pk_status, uint32_t n_pk, hipStream_t st);
 void launch_l0_msm(const DevBatch& B, hipStream_t st);
+// fused level 0: S from the subgroup test's sums (k_l0f_reduce, k_l0f_fold, k_l0f_horner)
+void launch_l0_fused_s(const DevBatch& B, hipStream_t st);
 void launch_l0_check(const DevBatch& B, hipStream_t st);
 // level 0's P-chunk and S Miller products on hexads (k_miller_hex.hip)
 void launch_l0_miller_hex(const DevBatch& B, hipStream_t st);

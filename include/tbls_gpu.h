@@ -95,7 +95,10 @@ typedef struct {
                            * invalid partials passes 0.3 % / 3 % (TBG_RLC_AUTO_*)   */
   uint64_t rlc_seed;      /* 0: fresh OS randomness per batch; else fixed (tests).
                            * Keys the RLC scalars only: the batched subgroup test's
-                           * combinations always take fresh OS randomness            */
+                           * combinations always take fresh OS randomness.  While
+                           * that test runs, level 0 derives its scalars from the
+                           * test's digits, so a fixed rlc_seed does NOT fix level
+                           * 0's scalars then (it still fixes the group levels')     */
   uint32_t rlc_chunk;     /* duties per Miller-loop quad inside a group (0 -> 4)  */
   uint32_t streams_per_slot; /* 1 (0 -> 1) or 2: hash_to_G2 on its own stream   */
   uint32_t rlc_batch;     /* level 0, the whole device batch as ONE check (RLC mode):

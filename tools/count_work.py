@@ -157,9 +157,39 @@ def main():
     launch_dvs = 16 * 10000  # bench default: 16 batches of 10k DVs per launch
     unit_3of4_l0_alone = (4 * decode + hash_ + lines_h + 4 * l0_partial + duty_sum_p4 + l0_per_group / G + agg
                           + l0_per_launch / launch_dvs)
-    # the default chain: decode + the batched subgroup test instead of one
-    # subgroup test per signature
-    unit_3of4_l0 = unit_3of4_l0_alone - 4 * decode + 4 * decode_sgb
+    # the bucket-MSM chain with the batched subgroup test (before the fused level 0)
+    unit_3of4_l0_msm = unit_3of4_l0_alone - 4 * decode + 4 * decode_sgb
+    # Fused level 0 (round 7; bls_rlc.h top, k_msm.hip k_l0f_*): with the
+    # batched subgroup test on, S comes from that test's sums.  Per partial:
+    # one more mixed addition (the unweighted sum T, k_sgb_bucket) and the
+    # 10 + 8-window key product (no bucket additions); per launch the sums of
+    # the 18 Q_k slots and T's slices over the groups (k_l0f_reduce / _fold:
+    # one addition per point) and the Horner chain (k_l0f_horner).  Probes:
+    # tests/l0fused/l0fused_host.cpp built with TBG_COUNT_OPS.
+    fsrc = os.path.join(ROOT, "tests", "l0fused", "l0fused_host.cpp")
+    flib_path = os.path.join(ROOT, "tests", "l0fused", "libl0fused_count.so")
+    subprocess.check_call(["/opt/rocm/llvm/bin/clang++", "-O1", "-std=c++17", "-fPIC", "-shared", "-DTBG_COUNT_OPS",
+                           "-Wno-pass-failed", fsrc, "-o", flib_path])
+    flib = ctypes.CDLL(flib_path)
+    flib.l0f_hc_count_get.restype = ctypes.c_ulonglong
+
+    def fmeasure(fn, *a):
+        flib.l0f_hc_count_reset()
+        r = fn(*a)
+        return flib.l0f_hc_count_get(), r
+
+    assert flib.l0f_hc_probe_setup(pks[0], sigs[0]) == 0
+    digit_sets = [[6] * 18, [-6] * 18, [1, -2, 3, -4, 5, -6, 0, 2, -1, 4, -3, 6, -5, 1, 0, -2, 3, -6]]
+    l0f_g1 = sum(fmeasure(flib.l0f_hc_probe_g1, (ctypes.c_int32 * 18)(*c))[0] for c in digit_sets) / len(digit_sets)
+    l0f_horner, _ = fmeasure(flib.l0f_hc_probe_horner)
+    n_sg = -(-4 * launch_dvs // sgb_m)
+    l0f_reduce = n_sg * (sgb_k + sgb_m // 32) * g2_add
+    l0f_per_launch = l0f_reduce + l0f_horner + lines_h + s_quad + final1
+    sgb_bucket_t = sgb_bucket + madd
+    decode_sgb_fused = decode_sgb + madd
+    l0f_partial = l0f_g1  # (no bucket additions: the signature side is the subgroup test's)
+    unit_3of4_l0 = (4 * decode_sgb_fused + hash_ + lines_h + 4 * l0f_partial + duty_sum_p4 + l0_per_group / G + agg
+                    + l0f_per_launch / launch_dvs)
     # every candidate but the first of each group is randomised: (4 G - 1) / G per duty
     unit_3of4_rlc = (4 * decode + hash_ + lines_h + (4 * G - 1) / G * rlc_partial + duty_sum4 + group_lines8 / G
                      + rlc_check_per_group / G + agg)
@@ -180,6 +210,9 @@ def main():
                  "g2_add": g2_add, "quad_mul": qmul, "l0_s_quad": s_quad, "final_exp_quad": final1,
                  "l0_chunk_base": round(chunk_base), "l0_chunk_per_duty": round(chunk_per_duty),
                  "unit_3of4_l0": round(unit_3of4_l0), "l0_launch_dvs": launch_dvs,
+                 "unit_3of4_l0_bucket_msm": round(unit_3of4_l0_msm),
+                 "l0f_partial": round(l0f_partial), "l0f_key_product": round(l0f_g1), "l0f_horner": l0f_horner,
+                 "l0f_per_launch": round(l0f_per_launch),
                  "unit_3of4_l0_subgroup_alone": round(unit_3of4_l0_alone),
                  "decode_sig_batched_subgroup": round(decode_sgb), "sgb_per_partial": round(sgb_per_partial),
                  "unit_3of4_rlc": round(unit_3of4_rlc), "unit_3of4_each": unit_3of4,
@@ -202,7 +235,7 @@ def main():
         "kernels": {
             "k_decode_sigs": {"per": "partial", "mads": round(k_decode)},
             "k_subgroup_sigs": {"per": "partial", "mads": round(k_subgroup)},
-            "k_sgb_bucket": {"per": "partial", "mads": round(sgb_bucket)},
+            "k_sgb_bucket": {"per": "partial", "mads": round(sgb_bucket_t)},  # (with the fused level 0's sum T)
             "k_sgb_fold": {"per": "partial", "mads": round(sgb_fold)},
             "k_sgb_combine": {"per": "partial", "mads": round(sgb_combine)},
             "k_sgb_test": {"per": "partial", "mads": round(sgb_test)},
@@ -213,7 +246,11 @@ def main():
             "k_hash_clear_fin": {"per": "message", "mads": round(k_clear_fin)},
             "k_hash_affine": {"per": "message", "mads": round(k_g2_aff)},
             "k_lines_h": {"per": "message", "mads": round(lines_h)},
-            "k_rlc_g1_l0": {"per": "partial", "mads": round(k_g1_l0)},
+            "k_rlc_g1_l0": {"per": "partial", "mads": round(l0f_g1)},  # (fused: 18 doublings + 18 additions)
+            "k_l0f_reduce": {"per": "launch", "mads": round(l0f_reduce)},
+            "k_l0f_horner": {"per": "launch", "mads": l0f_horner},
+            # without the batched subgroup test: the bucket MSM (k_rlc_g1_l0 then costs k_rlc_g1_l0_msm)
+            "k_rlc_g1_l0_msm": {"per": "partial", "mads": round(k_g1_l0)},
             "k_msm_bucket_part": {"per": "partial", "mads": round(4 * k_msm_entry)},
             "k_msm_bucket": {"per": "launch", "mads": round(bucket_scales + 32768 * (4 - 1) * g2_add)},
             "k_rlc_duty_sum<DSUM_L0_P>": {"per": "duty", "mads": round(duty_sum_p4)},
