@@ -1188,3 +1188,63 @@ int hc_sgb_group(const uint8_t* sigs96, int n, const uint32_t* seed8, uint32_t i
   return mask;
 }
 }
+
+// ---------------------------------------------------------------------------
+// Raw-limb exports for the directed operand lists (tests/edge_operands.py,
+// test_devcheck_operands.py): the operations tests/devcheck runs on the GPU,
+// with the same operation codes, on limbs exactly as given -- no Montgomery
+// conversion, lazy and redundant forms included -- so TBG_BOUNDS_CHECK vets
+// every operand before the device sees it.
+extern "C" {
+static Fp raw_in(const uint32_t* l) {
+  Fp r;
+  for (int i = 0; i < NL; ++i) r.l[i] = l[i];
+  return r;
+}
+// op: mul, mul2, sqr, add, sub, addl_mul, subl_mul, neg, negl_mul, mul_small,
+// reduce, canon, inv, inv_fermat, from_signed (0..14); -1 for an unknown op
+int hc_fp_op_raw(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t k,
+                 uint32_t* out) {
+  Fp r;
+  switch (op) {
+    case 0: r = fp_mul(raw_in(a), raw_in(b)); break;
+    case 1: r = fp_mul2(raw_in(a), raw_in(b), raw_in(c), raw_in(d)); break;
+    case 2: r = fp_sqr(raw_in(a)); break;
+    case 3: r = fp_add(raw_in(a), raw_in(b)); break;
+    case 4: r = fp_sub(raw_in(a), raw_in(b)); break;
+    case 5: r = fp_mul(fp_add_l(raw_in(a), raw_in(b)), raw_in(c)); break;
+    case 6: r = fp_mul(fp_sub_l(raw_in(a), raw_in(b)), raw_in(c)); break;
+    case 7: r = fp_neg(raw_in(a)); break;
+    case 8: r = fp_mul(raw_in(a), fp_neg_l(raw_in(b))); break;
+    case 9: r = fp_mul_small(raw_in(a), k); break;
+    case 10: r = fp_reduce(raw_in(a)); break;
+    case 11: r = fp_canon(raw_in(a)); break;
+    case 12: r = fp_inv(raw_in(a)); break;
+    case 13: r = fp_inv_fermat(raw_in(a)); break;
+    case 14: r = fp_from_signed((const int32_t*)a); break;
+    default: return -1;
+  }
+  for (int i = 0; i < NL; ++i) out[i] = r.l[i];
+  return 0;
+}
+// op: row_mul, row_mul2, row_reduce(r_norm(.)), r_norm (0..3); all 16 lanes out
+int hc_row_op_raw(int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, int32_t* out16) {
+  R32 r;
+  switch (op) {
+    case 0: r = row_mul(row_in(a), row_in(b)); break;
+    case 1: r = row_mul2(row_in(a), row_in(b), row_in(c), row_in(d)); break;
+    case 2: r = row_reduce(r_norm(row_in(a))); break;
+    case 3: r = r_norm(row_in(a)); break;
+    default: return -1;
+  }
+  for (int k = 0; k < 16; ++k) out16[k] = r.v[k];
+  return 0;
+}
+// g2_lines of an affine point (x.c0 x.c1 y.c0 y.c1, 14 raw limbs each) with
+// -g1 folded in: LINES_WORDS words, the reference of the row / pair line tests
+void hc_g2_lines_raw(const uint32_t* q, uint32_t* out) {
+  const G2A Q{{raw_in(q), raw_in(q + NL)}, {raw_in(q + 2 * NL), raw_in(q + 3 * NL)}};
+  const Fp nx = fp_reduce(fp_neg(fp_from_const(G1_X))), y = fp_from_const(G1_NEG_Y);
+  g2_lines(Q, nx, y, out);
+}
+}
