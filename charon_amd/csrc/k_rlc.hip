@@ -179,7 +179,7 @@ __global__ void TBG_LAUNCH_N(TBG_HEX_WAVES) k_rlc_group_final(DevBatch B) {
   uint32_t d0 = g * G, d1 = min(d0 + G, B.n_duties);
   for (uint32_t d = d0; d < d1; ++d) {
     if (B.dv_state[d] == RLC_COMBINED && B.h_status[B.duty_msg[d]] != 0) {
-      if (lead) B.grp_state[g] = GRP_FAIL;  // resolved per chunk / duty
+      if (lead) B.grp_state[g] = B.sets ? GRP_BAD : GRP_FAIL;  // resolved per chunk / duty (a set launch: its set fails)
       return;
     }
   }
@@ -205,7 +205,7 @@ __global__ void TBG_LAUNCH_N(TBG_HEX_WAVES) k_rlc_group_final(DevBatch B) {
       return;
     }
   }
-  if (lead) B.grp_state[g] = ok ? GRP_OK : GRP_FAIL;
+  if (lead) B.grp_state[g] = ok ? GRP_OK : B.sets ? GRP_BAD : GRP_FAIL;
 }
 
 // ------------------------------------------------------------------ level 0
@@ -893,6 +893,7 @@ static void fb_passes(const DevBatch& B, uint32_t max_entries, F&& body, bool ma
 void launch_rlc_prepare(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff, const G1A* pk_tab,
                         const int32_t* pk_status, uint32_t n_pk, hipStream_t st,
                         void (*after_keys)(const DevBatch&, hipStream_t)) {
+  if (B.sets) launch_set_init(B, st);
   if (!B.n_duties) return;
   if (B.rlc_group == 0) {
     if (B.n_partials) TBG_KLAUNCH(k_list_all_partials, grid_for(B.n_partials), dim3(kBlock), st, B, pk_status, n_pk);
@@ -922,6 +923,44 @@ void launch_rlc_prepare(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff
   TBG_KLAUNCH(k_rlc_group_lines, grid_for(n_groups), dim3(kBlock), st, B);
 #endif
   launch_lines_fold(B, FOLD_GROUPS, n_groups, st);
+}
+
+// After the group checks of a plain launch: every failed group is narrowed to
+// its invalid partials (levels 1g, 1.5, 1.5b, 2b; what they cannot pin down
+// goes to level 3's list).  A set launch runs none of this (k_sets.hip).
+static void launch_narrowing(const DevBatch& B, const G1A* pk_aff, uint32_t n_groups, uint32_t nch, hipStream_t st) {
+  TBG_KLAUNCH(k_rlc_resolve_groups, grid_for(B.n_duties), dim3(kBlock), st, B);
+#if TBG_GMSM
+  // the failed groups' r_i s_i and S_d, which every deeper level reads
+  launch_gm_failed_partials(B, pk_aff, st);
+  TBG_KLAUNCH(k_rlc_duty_sum<DSUM_FALLBACK_S>, duty_grid(B), dim3(BINV_BLOCK), st, B);
+#endif
+  if (B.rlc_group > 1) {
+    // level 1g before the chunks: its unresolved groups add to the chunk list
+    uint32_t W = 1;
+    while (W < B.rlc_group) W <<= 1;
+    TBG_KLAUNCH(k_rlc_gident_lines, grid_for(n_groups * W), dim3(kBlock), st, B);
+    fb_passes(B, n_groups, [&](const DevBatch& P, uint32_t n) {
+      launch_lines_fold(P, FOLD_GID, n, st);
+      TBG_KLAUNCH(k_rlc_gident_miller, grid_for(hex_threads(n * (nch + 1))), dim3(kBlock), st, P);
+      TBG_KLAUNCH(k_rlc_gident_check, grid_for(hex_threads(n)), dim3(kBlock), st, P);
+    });
+    TBG_KLAUNCH(k_rlc_chunk_lines, grid_for(n_groups * nch), dim3(kBlock), st, B);
+    fb_passes(B, n_groups * nch, [&](const DevBatch& P, uint32_t n) {
+      launch_lines_fold(P, FOLD_CHUNKS, n, st);
+      TBG_KLAUNCH(k_rlc_check_chunks, grid_for(hex_threads(n)), dim3(kBlock), st, P);
+    });
+    TBG_KLAUNCH(k_rlc_cident_lines, grid_for(n_groups * nch), dim3(kBlock), st, B);
+    fb_passes(B, n_groups * nch, [&](const DevBatch& P, uint32_t n) {
+      launch_lines_fold(P, FOLD_CID, n, st);
+      TBG_KLAUNCH(k_rlc_cident_check, grid_for(hex_threads(n)), dim3(kBlock), st, P);
+    });
+    TBG_KLAUNCH(k_rlc_ident_lines, grid_for(B.n_duties), dim3(kBlock), st, B);
+    fb_passes(B, B.n_duties, [&](const DevBatch& P, uint32_t n) {
+      launch_lines_fold(P, FOLD_IDENT, n, st);
+      TBG_KLAUNCH(k_rlc_ident_check, grid_for(hex_threads(n)), dim3(kBlock), st, P);
+    }, true);
+  }
 }
 
 void launch_rlc_check(const DevBatch& B0, const G1A* pk_aff, const G1A* xpk_aff, const G1A* pk_tab,
@@ -976,38 +1015,10 @@ void launch_rlc_check(const DevBatch& B0, const G1A* pk_aff, const G1A* xpk_aff,
       launch_groups_miller_hex(B, st);
     }
     TBG_KLAUNCH(k_rlc_group_final, grid_for(hex_threads(n_groups)), dim3(kBlock), st, B);
-    TBG_KLAUNCH(k_rlc_resolve_groups, grid_for(B.n_duties), dim3(kBlock), st, B);
-#if TBG_GMSM
-    // the failed groups' r_i s_i and S_d, which every deeper level reads
-    launch_gm_failed_partials(B, pk_aff, st);
-    TBG_KLAUNCH(k_rlc_duty_sum<DSUM_FALLBACK_S>, duty_grid(B), dim3(BINV_BLOCK), st, B);
-#endif
-    if (B.rlc_group > 1) {
-      // level 1g before the chunks: its unresolved groups add to the chunk list
-      uint32_t W = 1;
-      while (W < B.rlc_group) W <<= 1;
-      TBG_KLAUNCH(k_rlc_gident_lines, grid_for(n_groups * W), dim3(kBlock), st, B);
-      fb_passes(B, n_groups, [&](const DevBatch& P, uint32_t n) {
-        launch_lines_fold(P, FOLD_GID, n, st);
-        TBG_KLAUNCH(k_rlc_gident_miller, grid_for(hex_threads(n * (nch + 1))), dim3(kBlock), st, P);
-        TBG_KLAUNCH(k_rlc_gident_check, grid_for(hex_threads(n)), dim3(kBlock), st, P);
-      });
-      TBG_KLAUNCH(k_rlc_chunk_lines, grid_for(n_groups * nch), dim3(kBlock), st, B);
-      fb_passes(B, n_groups * nch, [&](const DevBatch& P, uint32_t n) {
-        launch_lines_fold(P, FOLD_CHUNKS, n, st);
-        TBG_KLAUNCH(k_rlc_check_chunks, grid_for(hex_threads(n)), dim3(kBlock), st, P);
-      });
-      TBG_KLAUNCH(k_rlc_cident_lines, grid_for(n_groups * nch), dim3(kBlock), st, B);
-      fb_passes(B, n_groups * nch, [&](const DevBatch& P, uint32_t n) {
-        launch_lines_fold(P, FOLD_CID, n, st);
-        TBG_KLAUNCH(k_rlc_cident_check, grid_for(hex_threads(n)), dim3(kBlock), st, P);
-      });
-      TBG_KLAUNCH(k_rlc_ident_lines, grid_for(B.n_duties), dim3(kBlock), st, B);
-      fb_passes(B, B.n_duties, [&](const DevBatch& P, uint32_t n) {
-        launch_lines_fold(P, FOLD_IDENT, n, st);
-        TBG_KLAUNCH(k_rlc_ident_check, grid_for(hex_threads(n)), dim3(kBlock), st, P);
-      }, true);
-    }
+    // a set launch: a failed group fails its set, nothing is narrowed (no r_i s_i
+    // of the failed groups, no level 1g / 1.5 / 1.5b / 2b)
+    if (B.sets) launch_set_resolve(B, st);
+    else launch_narrowing(B, pk_aff, n_groups, nch, st);
   }
   if (B.n_partials) {
     fb_passes(B, B.n_partials, [&](const DevBatch& P, uint32_t n) {
@@ -1015,6 +1026,7 @@ void launch_rlc_check(const DevBatch& B0, const G1A* pk_aff, const G1A* xpk_aff,
       TBG_KLAUNCH(k_verify_list, grid_for(hex_threads(n)), dim3(kBlock), st, P, pk_aff);
     }, true);
   }
+  if (B.sets) launch_set_status(B, st);
 }
 
 }  // namespace tbg

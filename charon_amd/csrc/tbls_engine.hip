@@ -105,6 +105,10 @@ struct Slot {
   tbg::DevBatch last{};        // the batch as its last run launched it (a replay's prefix and shape):
                                // what tbg_fetch_stats / _fallback / _shape / _subgroup describe
   size_t w_out = 0;
+  // a set launch (tbg_submit_sets): its one part spans the padded device batch
+  bool sets = false;
+  uint32_t n_sets = 0;
+  size_t o_sets = 0;           // set_status in the output image
 };
 
 }  // namespace
@@ -565,7 +569,24 @@ static Slot* find_ticket(tbg_ctx* c, tbg_ticket t, bool want_pending, Part** par
   return nullptr;
 }
 
+static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches, tbg_ticket* tickets,
+                       const uint32_t* set_first, uint32_t n_sets);
+
 int tbg_submit(tbg_ctx* c, const tbg_batch* b, tbg_ticket* ticket) { return tbg_submit_group(c, &b, 1, ticket); }
+
+int tbg_submit_group(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches, tbg_ticket* tickets) {
+  return submit_impl(c, bs, n_batches, tickets, nullptr, 0);
+}
+
+int tbg_submit_sets(tbg_ctx* c, const tbg_batch* b, const uint32_t* set_first, uint32_t n_sets, tbg_ticket* ticket) {
+  if (!c || !b || !set_first || !ticket) return TBG_E_INVALID_ARG;
+  int rc = validate(b);
+  if (rc != TBG_OK) return rc;
+  if (b->op != TBG_OP_VERIFY || set_first[0] != 0 || set_first[n_sets] != b->n_duties) return TBG_E_INVALID_ARG;
+  for (uint32_t k = 0; k < n_sets; ++k)
+    if (set_first[k + 1] < set_first[k]) return TBG_E_INVALID_ARG;
+  return submit_impl(c, &b, 1, ticket, set_first, n_sets);
+}
 
 // Level-0 launch shape.  The level-0 Miller kernel's
 // waves are long -- one hexad = the whole 68-step loop over C duties -- and
@@ -665,7 +686,20 @@ static bool sgb_plan(double rho, uint32_t& m) {
   return best < 0.95;
 }
 
-int tbg_submit_group(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches, tbg_ticket* tickets) {
+// Device duties of a set launch at group size G: every non-empty set starts on
+// a multiple of G (the duties between are empty padding), so no level-1 group
+// holds duties of two sets.
+static uint64_t sets_padded(const uint32_t* set_first, uint32_t n_sets, uint32_t G) {
+  uint64_t e = 0;
+  for (uint32_t k = 0; k < n_sets; ++k) {
+    const uint32_t n = set_first[k + 1] - set_first[k];
+    if (n) e = (e + G - 1) / G * G + n;
+  }
+  return e;
+}
+
+static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches, tbg_ticket* tickets,
+                       const uint32_t* set_first, uint32_t n_sets) {
   if (!c || !bs || !tickets || n_batches == 0) return TBG_E_INVALID_ARG;
   int rc;
   for (uint32_t k = 0; k < n_batches; ++k) {
@@ -699,8 +733,20 @@ int tbg_submit_group(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches,
       if (!x.express && !x.busy && (!s || x.ticket < s->ticket)) s = &x;
   if (!s) return TBG_E_BUSY;
 
-  const uint32_t nd = (uint32_t)nd64, np = (uint32_t)np64, nm = (uint32_t)nm64;
+  const uint32_t np = (uint32_t)np64, nm = (uint32_t)nm64;
   const size_t msg_bytes = (size_t)mb64;
+  if (c->rlc_auto)
+    c->rlc_group = c->invalid_ema < TBG_RLC_AUTO_TO8 ? 16 : c->invalid_ema < TBG_RLC_AUTO_TO4 ? 8 : 4;
+  uint32_t G = verify ? c->rlc_group : 0;
+  if (set_first) {
+    // An unconfigured group size shrinks (to 8, then 4) while the sets'
+    // padding would pass 1/8 of the duties: a launch of small sets keeps its
+    // groups full instead of checking mostly padding.
+    while (c->rlc_auto && G > 4 && sets_padded(set_first, n_sets, G) > nd64 + nd64 / 8) G /= 2;
+    nd64 = sets_padded(set_first, n_sets, G ? G : 1);  // (>= the caller's duties: validate() wants one at least)
+    if (nd64 > 0x7FFFFFFFull) return TBG_E_INVALID_ARG;
+  }
+  const uint32_t nd = (uint32_t)nd64;
 
   // ---- input arena layout (16-byte aligned sections) ----
   size_t o = 0;
@@ -714,6 +760,7 @@ int tbg_submit_group(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches,
   size_t o_sigs = sec(96ull * np);
   size_t o_ids = sec(np);
   size_t o_pk = sec(4ull * np);
+  size_t o_dset = sec(set_first ? 4ull * nd : 0);
   size_t in_bytes = o;
   // ---- work/output arena ----
   o = 0;
@@ -728,15 +775,13 @@ int tbg_submit_group(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches,
   const uint32_t fb_w = verify ? std::max<uint32_t>(1u, std::min<uint32_t>(c->fb_window, np)) : 0u;
   size_t w_sl = sec(4ull * LINES_WORDS * fb_w);
   size_t w_hl = sec(4ull * LINES_WORDS * nm);
-  if (c->rlc_auto)
-    c->rlc_group = c->invalid_ema < TBG_RLC_AUTO_TO8 ? 16 : c->invalid_ema < TBG_RLC_AUTO_TO4 ? 8 : 4;
-  uint32_t G = verify ? c->rlc_group : 0;
   // Level 0 while the collected batches are clean (or as configured): one
   // failed level-0 check costs its own work on top of the group levels.
   const bool l0 = G != 0 && np < (1u << 28) &&
                   (c->rlc_batch == TBG_RLC_L0_ON || (c->rlc_batch == TBG_RLC_L0_AUTO && c->invalid_ema < TBG_RLC_AUTO_L0));
   uint32_t C = c->rlc_chunk;
-  if (l0 && c->chunk_auto) l0_shape(nd, c->n_simd, c->rlc_auto && G == 16, G, C, l0_fits_any);
+  // (a set launch keeps its G: the sets are padded to it)
+  if (l0 && c->chunk_auto) l0_shape(nd, c->n_simd, !set_first && c->rlc_auto && G == 16, G, C, l0_fits_any);
   if (C > G) C = G ? G : 1;
   const uint32_t ng = G ? (nd + G - 1) / G : 0;
   const uint32_t nch = G ? (G + C - 1) / C : 0;
@@ -811,6 +856,7 @@ int tbg_submit_group(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches,
   size_t w_pst = sec(4ull * np);
   size_t w_dst = sec(4ull * nd);
   size_t w_agg = sec(96ull * nd);
+  size_t w_sst = sec(set_first ? 4ull * ((size_t)n_sets + SET_TAIL) : 0);
   size_t work_bytes = o;
   size_t out_bytes = work_bytes - w_out;
 
@@ -876,8 +922,44 @@ int tbg_submit_group(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches,
       memcpy(h + o_ids + P, b->identifiers, bnp);
     }
   };
+  // A set launch (one caller batch): the duties move to their padded places,
+  // set k's first on a multiple of Gp; a padding duty is empty (no partials,
+  // message 0), which k_rlc_duty_sum leaves RLC_NONE.  Partials and messages
+  // keep their indices.
+  auto pack_sets = [&]() {
+    const tbg_batch* b = bs[0];
+    const uint32_t Gp = G ? G : 1;
+    uint32_t* dset = (uint32_t*)(h + o_dset);
+    if (msg_bytes) memcpy(h + o_msgs, b->msgs, msg_bytes);
+    memcpy(msg_off, b->msg_off, 4ull * nm);
+    if (np) {
+      memcpy(h + o_pk, b->pubkey_ids, 4ull * np);
+      memcpy(h + o_sigs, b->sigs, 96ull * np);
+      memcpy(h + o_ids, b->identifiers, np);
+    }
+    uint32_t e = 0;
+    for (uint32_t k = 0; k < n_sets; ++k) {
+      const uint32_t a = set_first[k], z = set_first[k + 1];
+      if (a == z) continue;
+      for (; e % Gp; ++e) {
+        duty_first[e] = b->duty_first[a];
+        duty_msg[e] = 0;
+        dset[e] = k;
+      }
+      for (uint32_t d = a; d < z; ++d, ++e) {
+        duty_first[e] = b->duty_first[d];
+        duty_msg[e] = b->duty_msg[d];
+        dset[e] = k;
+        for (uint32_t j = b->duty_first[d]; j < b->duty_first[d + 1]; ++j) pd[j] = e;
+      }
+    }
+    memset(thr, 0, 4ull * nd);
+    parts[0].nd = nd;
+  };
   const uint32_t workers = (np >= (1u << 16) && n_batches > 1) ? std::min<uint32_t>(n_batches, 8) : 1;
-  if (workers == 1) {
+  if (set_first) {
+    pack_sets();
+  } else if (workers == 1) {
     for (uint32_t k = 0; k < n_batches; ++k) pack(k);
   } else {
     std::vector<std::thread> th;
@@ -994,6 +1076,13 @@ int tbg_submit_group(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches,
   B.partial_status = (int32_t*)(dw + w_pst);
   B.duty_status = (int32_t*)(dw + w_dst);
   B.agg = dw + w_agg;
+  if (set_first) {
+    B.sets = 1;
+    B.n_sets = n_sets;
+    B.duty_set = (const uint32_t*)(di + o_dset);
+    B.set_status = (int32_t*)(dw + w_sst);
+    B.gident = 0;  // (no level 1g: a failed group is not narrowed)
+  }
   B.rlc_batch = l0 ? 1u : 0u;
   B.msm_r = (uint64_t*)(dw + w_mr);
   B.msm_off = (uint32_t*)(dw + w_moff);
@@ -1064,6 +1153,9 @@ int tbg_submit_group(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches,
   s->B = B;
   s->last = B;
   s->w_out = w_out;
+  s->sets = set_first != nullptr;
+  s->n_sets = set_first ? n_sets : 0;
+  s->o_sets = w_sst - w_out;
   return TBG_OK;
 }
 
@@ -1096,12 +1188,21 @@ static void part_done(Slot* s, Part* q) {
   s->busy = any;
 }
 
-int tbg_collect(tbg_ctx* c, tbg_ticket t, int32_t* pst, int32_t* dst, uint8_t* agg, int block) {
+// A set launch's slice of the output image: the sets' statuses, and the
+// partial statuses (partials keep their caller indices in the padded batch).
+static void copy_sets(const Slot* s, int32_t* sst, int32_t* pst) {
+  if (sst) memcpy(sst, s->h_out + s->o_sets, 4ull * s->n_sets);
+  if (pst) memcpy(pst, s->h_out, 4ull * s->n_partials);  // (partial statuses lead the output image)
+}
+
+// tbg_collect (sets = false) and tbg_collect_sets (sets = true: sst / pst).
+static int collect_impl(tbg_ctx* c, tbg_ticket t, int32_t* pst, int32_t* dst, uint8_t* agg, int32_t* sst, bool sets,
+                        int block) {
   if (!c) return TBG_E_INVALID_ARG;
   std::unique_lock<std::mutex> lk(c->mu);
   Part* q = nullptr;
   Slot* s = find_ticket(c, t, true, &q);
-  if (!s || q->collecting) return TBG_E_TICKET;
+  if (!s || q->collecting || s->sets != sets) return TBG_E_TICKET;
   HIP_TRY(hipSetDevice(c->device));
   hipError_t e = hipEventQuery(s->done);
   if (e == hipErrorNotReady) {
@@ -1126,8 +1227,15 @@ int tbg_collect(tbg_ctx* c, tbg_ticket t, int32_t* pst, int32_t* dst, uint8_t* a
     return TBG_E_DEVICE;
   }
   const auto t_gather = std::chrono::steady_clock::now();
-  copy_part(s, *q, pst, dst, agg);
-  if (s->op != TBG_OP_AGGREGATE && q->np) {  // the adaptive group size's and level 0's input
+  if (sets) copy_sets(s, sst, pst);
+  else copy_part(s, *q, pst, dst, agg);
+  if (sets) {
+    // every candidate of a failed group counts as invalid: an upper bound of
+    // the invalid share, so level 0 switches off under bad sets as it does
+    // under bad partials
+    s->seen_bad += (uint32_t)((const int32_t*)(s->h_out + s->o_sets))[s->n_sets + SET_BAD];
+    s->seen_total += q->np;
+  } else if (s->op != TBG_OP_AGGREGATE && q->np) {  // the adaptive group size's and level 0's input
     const int32_t* st = (const int32_t*)s->h_out;  // partial statuses lead the output region
     uint32_t bad = 0;
     for (uint32_t i = 0; i < q->np; ++i) bad += st[q->p0 + i] == TBG_PS_INVALID ? 1u : 0u;
@@ -1159,6 +1267,14 @@ int tbg_collect(tbg_ctx* c, tbg_ticket t, int32_t* pst, int32_t* dst, uint8_t* a
     s->seen_nsub = s->seen_dec = 0;
   }
   return TBG_OK;
+}
+
+int tbg_collect(tbg_ctx* c, tbg_ticket t, int32_t* pst, int32_t* dst, uint8_t* agg, int block) {
+  return collect_impl(c, t, pst, dst, agg, nullptr, false, block);
+}
+
+int tbg_collect_sets(tbg_ctx* c, tbg_ticket t, int32_t* set_status, int32_t* partial_status, int block) {
+  return collect_impl(c, t, partial_status, nullptr, nullptr, set_status, true, block);
 }
 
 int tbg_run(tbg_ctx* c, const tbg_batch* b, int32_t* pst, int32_t* dst, uint8_t* agg) {
@@ -1210,7 +1326,7 @@ int tbg_replay_plan(tbg_ctx* c, const tbg_ticket* tickets, const uint32_t* n_par
       bool all_l0 = true;
       for (uint32_t k = k0; k < k1; ++k) {
         nd += bs[k].n_duties;
-        all_l0 = all_l0 && bs[k].rlc_batch && bs[k].rlc_group >= 8;
+        all_l0 = all_l0 && bs[k].rlc_batch && bs[k].rlc_group >= 8 && !bs[k].sets;  // (sets are padded to their G)
       }
       // the cheapest shape every launch of the run can hold (round 6: the
       // candidates that one of them cannot are skipped, not the reshape)
@@ -1317,17 +1433,26 @@ int tbg_replay_multi(tbg_ctx* c, const tbg_ticket* tickets, uint32_t n_tickets, 
 
 int tbg_replay(tbg_ctx* c, tbg_ticket t, uint32_t iters, float* ms8) { return tbg_replay_multi(c, &t, 1, iters, ms8); }
 
-int tbg_fetch(tbg_ctx* c, tbg_ticket t, int32_t* pst, int32_t* dst, uint8_t* agg) {
+static int fetch_impl(tbg_ctx* c, tbg_ticket t, int32_t* pst, int32_t* dst, uint8_t* agg, int32_t* sst, bool sets) {
   if (!c) return TBG_E_INVALID_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   Part* q = nullptr;
   Slot* s = find_ticket(c, t, false, &q);
-  if (!s) return TBG_E_TICKET;
+  if (!s || s->sets != sets) return TBG_E_TICKET;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipMemcpyAsync(s->h_out, s->d_work + s->w_out, s->out_bytes, hipMemcpyDeviceToHost, s->st));
   HIP_TRY(hipStreamSynchronize(s->st));
-  copy_part(s, *q, pst, dst, agg);
+  if (sets) copy_sets(s, sst, pst);
+  else copy_part(s, *q, pst, dst, agg);
   return TBG_OK;
+}
+
+int tbg_fetch(tbg_ctx* c, tbg_ticket t, int32_t* pst, int32_t* dst, uint8_t* agg) {
+  return fetch_impl(c, t, pst, dst, agg, nullptr, false);
+}
+
+int tbg_fetch_sets(tbg_ctx* c, tbg_ticket t, int32_t* set_status, int32_t* partial_status) {
+  return fetch_impl(c, t, partial_status, nullptr, nullptr, set_status, true);
 }
 
 int tbg_fetch_stats(tbg_ctx* c, tbg_ticket t, uint32_t* out4) {

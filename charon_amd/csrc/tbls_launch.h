@@ -205,10 +205,23 @@ struct DevBatch {
   int32_t* partial_status;
   int32_t* duty_status;
   uint8_t* agg;        // [n_duties][96]
+  // set launch (tbg_submit_sets, k_sets.hip): per set, whether every member
+  // verifies; a failed group fails its set with no narrowing.  Every set
+  // starts on a multiple of rlc_group (empty padding duties, packed by the
+  // host), so a level-1 group lies inside one set.
+  uint32_t sets;              // 1: a set launch
+  uint32_t n_sets;
+  const uint32_t* duty_set;   // [n_duties] the duty's set
+  int32_t* set_status;        // [n_sets + SET_TAIL] TBG_SS_* per set (outputs), then SET_BAD, SET_ANY
 };
+// set_status's tail words: SET_BAD counts the partials left invalid or
+// unverified (every candidate of a failed group: the adaptive policies' upper
+// bound), SET_ANY the partials whose code is not VALID (0: nothing to rewrite)
+enum SetTail : int { SET_BAD = 0, SET_ANY = 1, SET_TAIL = 2 };
 
 enum RlcState : int32_t { RLC_NONE = 0, RLC_COMBINED = 1, RLC_EACH = 2 };
-enum GroupState : int32_t { GRP_EMPTY = 0, GRP_LINES = 1, GRP_OK = 2, GRP_FAIL = 3, GRP_GID = 4 };  // GRP_GID: at level 1g
+enum GroupState : int32_t { GRP_EMPTY = 0, GRP_LINES = 1, GRP_OK = 2, GRP_FAIL = 3, GRP_GID = 4,  // GRP_GID: at level 1g
+                            GRP_BAD = 5 };  // a set launch's group whose check failed (GRP_FAIL: its sum was degenerate)
 // CNT_DUTIES: level-2b duties (id_list), CNT_PARTIALS: level-3 partials, CNT_AGG: [1/D] duties,
 // CNT_CHUNKS: level-1.5 chunks, CNT_CID: level-1.5b chunks, CNT_L0_BAD: level 0 cannot
 // hold (a degenerate sum, a duty checked per partial, an unusable H(m)), CNT_L0_OK: level 0 passed
@@ -388,6 +401,12 @@ void launch_rlc_prepare(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff
 void launch_rlc_check(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff, const G1A* pk_tab,
                       const int32_t* pk_status, uint32_t n_pk, hipStream_t st);
 void launch_lines_fold(const DevBatch& B, int kind, uint32_t max_entries, hipStream_t st);
+// set launches (k_sets.hip): set_status to VALID before the checks; after
+// level 1, k_set_resolve in place of k_rlc_resolve_groups; after level 3, the
+// sets' statuses and the partial statuses of the failed sets
+void launch_set_init(const DevBatch& B, hipStream_t st);
+void launch_set_resolve(const DevBatch& B, hipStream_t st);
+void launch_set_status(const DevBatch& B, hipStream_t st);
 // level 0 (k_msm.hip)
 void launch_pubkey_tables(const G1A* pk, const G1A* xpk, const int32_t* status, uint32_t n, G1A* tab, hipStream_t st);
 void launch_l0_keys(const DevBatch& B, const G1A* pk_tab, const int32_t* pk_status, uint32_t n_pk, hipStream_t st);

@@ -21,6 +21,8 @@ PS_ERR_FLAGS, PS_ERR_FIELD, PS_ERR_CURVE, PS_ERR_SUBGROUP, PS_ERR_IDENTITY, PS_E
 DS_OK, DS_NOT_AGGREGATED = 0, 1
 DS_INSUFFICIENT, DS_INSUFFICIENT_VALID = -20, -21
 DS_AGG_TOO_FEW, DS_AGG_DUPLICATE_ID, DS_AGG_IDENTITY, DS_DECODE = -22, -23, -24, -25
+# per-set status (TBG_SS_*, submit_sets): ERROR < INVALID < VALID
+SS_ERROR, SS_INVALID, SS_VALID = 30, 31, 32
 OP_VERIFY, OP_AGGREGATE, OP_VERIFY_AGGREGATE = 1, 2, 3
 NO_PUBKEY = 0xFFFFFFFF
 TIMING_KEYS = ["decode", "hash", "combine", "h_lines", "verify", "lagrange", "aggregate", "total"]
@@ -35,6 +37,7 @@ HOST_STAT_KEYS = ["submits", "partials_submitted", "pack_ns", "enqueue_ns", "col
 MULTI_HOST_STAT_KEYS = ["submits", "partials", "build_ns", "submit_wall_ns", "collects", "collect_wall_ns"] + \
     ["ctx_" + k for k in HOST_STAT_KEYS] + ["contexts", "reserved"]
 E_PENDING = -6
+E_INVALID_ARG, E_TICKET = -1, -7
 
 
 class EngineError(RuntimeError):
@@ -69,6 +72,12 @@ class BatchResult:
     partial_status: np.ndarray  # int32 [n_partials]
     duty_status: np.ndarray     # int32 [n_duties]
     agg: np.ndarray             # uint8 [n_duties, 96]
+
+
+@dataclass
+class SetsResult:
+    set_status: np.ndarray      # int32 [n_sets]: SS_*
+    partial_status: np.ndarray  # int32 [n_partials]: negative codes exact, PS_VALID in a VALID set, else PS_NOT_VERIFIED
 
 
 _serial = itertools.count(1)
@@ -195,6 +204,40 @@ class Engine:
 
     def run(self, op, duty_first, sigs, identifiers, **kw) -> BatchResult:
         return self.collect(self.submit(op, duty_first, sigs, identifiers, **kw))
+
+    # ------------------------------------------------------------ sets (all or nothing)
+    def submit_sets(self, set_first, duty_first, sigs, identifiers, **kw):
+        """A TBG_OP_VERIFY batch whose duties [set_first[k], set_first[k+1])
+        form set k (tbg_submit_sets): per set, whether every member verifies;
+        a failed set is not narrowed to its bad partial."""
+        b, keep, nd, np_ = self._batch(OP_VERIFY, duty_first, sigs, identifiers, **kw)
+        sf = _u32(set_first)
+        t = ctypes.c_uint64()
+        self._check(self._lib.tbg_submit_sets(self._h, ctypes.byref(b), _ptr(sf), len(sf) - 1, ctypes.byref(t)),
+                    "tbg_submit_sets")
+        self._keep[t.value] = (len(sf) - 1, np_)
+        return t.value
+
+    def collect_sets(self, ticket, block=True):
+        ns, np_ = self._keep[ticket]
+        ss = np.zeros(ns, dtype=np.int32)
+        ps = np.zeros(np_, dtype=np.int32)
+        rc = self._lib.tbg_collect_sets(self._h, ticket, _ptr(ss), _ptr(ps), 1 if block else 0)
+        if rc == E_PENDING:
+            return None
+        self._check(rc, "tbg_collect_sets")
+        del self._keep[ticket]
+        return SetsResult(ss, ps)
+
+    def run_sets(self, set_first, duty_first, sigs, identifiers, **kw) -> SetsResult:
+        return self.collect_sets(self.submit_sets(set_first, duty_first, sigs, identifiers, **kw))
+
+    def fetch_sets(self, ticket, n_sets, n_partials) -> SetsResult:
+        """A collected set ticket's current outputs (after a replay)."""
+        ss = np.zeros(n_sets, dtype=np.int32)
+        ps = np.zeros(n_partials, dtype=np.int32)
+        self._check(self._lib.tbg_fetch_sets(self._h, ticket, _ptr(ss), _ptr(ps)), "tbg_fetch_sets")
+        return SetsResult(ss, ps)
 
     def poll(self, ticket) -> bool:
         """True once the batch has finished (nothing is consumed)."""

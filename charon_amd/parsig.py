@@ -4,6 +4,8 @@
   Eth2Verifier               core/parsigex/parsigex.go:152-176 (NewEth2Verifier)
     .verify_set              parsigex.go:101-107: any failure drops the set
     .verify_sets             many peer sets, one GPU submit, per-set verdicts
+    .verify_sets_drop        the same verdicts from one all-or-nothing set launch
+                             (no narrowing to the failing partial)
   verify_partial_sigs        core/validatorapi/validatorapi.go:1052-1067 plus the
                              submitters' loops (e.g. :228-287): first failure
                              aborts the batch
@@ -120,6 +122,39 @@ class Eth2Verifier:
                 out[k] = r
         return out
 
+    def verify_sets_drop(self, sets):
+        """sets: [(duty, {pubkey: ParSignedData})].  Per set None or a
+        ParSigError, None exactly where verify_sets gives None -- from ONE
+        all-or-nothing set launch (tbg_submit_sets): a failed set is reported
+        as failed without the narrowing that finds its bad partial, which the
+        receive path never reads (parsigex.go:101-107 drops the set).  A
+        host-detected fault (unknown pubkey, bad share index, zero signature,
+        wrong length, unknown domain) keeps verify_sets' message and keeps the
+        set off the GPU; a GPU failure reads "invalid signature: set failed
+        verification (duty=...)".
+        Not for validatorapi's submitters (verify_partial_sigs): they return
+        the FIRST failure in input order, which this operation does not give;
+        verify_sets / verify_items / verify_partial_sigs stay as they are."""
+        sets = list(sets)
+        out = [None] * len(sets)
+        live, items = [], []
+        for k, (duty, pset) in enumerate(sets):
+            its = []
+            for pubkey, data in pset.items():
+                it = self._item(pubkey, data)
+                if isinstance(it, Exception):
+                    out[k] = it
+                    break
+                its.append(it)
+            if out[k] is None:
+                live.append(k)
+                items.append(its)
+        if live:
+            for k, r in zip(live, signing.verify_sets_batch(self.spec, items, self.engine)):
+                if r is not None:
+                    out[k] = ParSigError(f"invalid signature: {r} (duty={sets[k][0]})")
+        return out
+
     def verify_set(self, duty: Duty, pset: dict) -> None:
         r = self.verify_sets([(duty, pset)])[0]
         if r is not None:
@@ -129,10 +164,14 @@ class Eth2Verifier:
 class ParSigEx:
     """The receive side of parsigex.Handle (parsigex.go:80-114), batch-aware:
     ``handle_batch`` verifies many received peer sets with one GPU submit and
-    forwards only the sets that verify completely to the subscribers."""
+    forwards only the sets that verify completely to the subscribers.
+    ``drop_only=True`` takes the verdicts from the all-or-nothing set launch
+    (Eth2Verifier.verify_sets_drop): the same sets are forwarded, a dropped
+    set's error no longer names its failing partial."""
 
-    def __init__(self, verifier: Eth2Verifier):
+    def __init__(self, verifier: Eth2Verifier, drop_only: bool = False):
         self.verifier = verifier
+        self.drop_only = drop_only
         self.subs = []
 
     def subscribe(self, fn):
@@ -141,7 +180,7 @@ class ParSigEx:
     def handle_batch(self, sets):
         """Returns per set None (forwarded) or the error that dropped it."""
         sets = list(sets)
-        verdicts = self.verifier.verify_sets(sets)
+        verdicts = self.verifier.verify_sets_drop(sets) if self.drop_only else self.verifier.verify_sets(sets)
         for (duty, pset), err in zip(sets, verdicts):
             if err is None:
                 for sub in self.subs:

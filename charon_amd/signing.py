@@ -171,10 +171,12 @@ class VerifyItem:
 _ZERO_SIG = bytes(96)
 
 
-def verify_batch(spec: Spec, items, engine=None):
-    """signing.Verify over many items with one GPU submit.  Returns, per item,
-    None (valid) or the SigningError the reference would return."""
-    items = list(items)
+def _host_checks(spec: Spec, items):
+    """The rejections signing.Verify makes before any curve work (unknown
+    domain, malformed root, zero signature, wrong length) and the signing
+    roots of the rest in one native batch.  Returns (out, todo, gpu_items):
+    out[i] the item's SigningError or None, gpu_items[k] = (pk, msg, sig) of
+    item todo[k]."""
     out = [None] * len(items)
     todo, gpu_items = [], []
     # signing roots of every well-formed item in one native batch
@@ -205,6 +207,14 @@ def verify_batch(spec: Spec, items, engine=None):
             pk = tbls.PublicKey(bytes(pk))
         todo.append(i)
         gpu_items.append((pk, msg, tbls.Signature(sig)))
+    return out, todo, gpu_items
+
+
+def verify_batch(spec: Spec, items, engine=None):
+    """signing.Verify over many items with one GPU submit.  Returns, per item,
+    None (valid) or the SigningError the reference would return."""
+    items = list(items)
+    out, todo, gpu_items = _host_checks(spec, items)
     if gpu_items:
         res = tbls.verify_batch(gpu_items, engine)
         for i, r in zip(todo, res):
@@ -212,6 +222,36 @@ def verify_batch(spec: Spec, items, engine=None):
                 out[i] = SigningError("convert signature: " + str(r))
             elif not r:
                 out[i] = SigningError("invalid signature")
+    return out
+
+
+SET_FAILED = "set failed verification"
+
+
+def verify_sets_batch(spec: Spec, sets_of_items, engine=None):
+    """All-or-nothing signing.Verify over sets of VerifyItems with one GPU set
+    launch (tbls.verify_sets_batch).  Per set returns None (every item valid)
+    or a SigningError: the first host-side rejection of verify_batch (unknown
+    domain, zero signature, wrong length) -- such a set has failed already and
+    none of its items reaches the GPU -- or SET_FAILED, which does not say
+    which item failed: the set launch does not narrow a failed set."""
+    sets = [list(s) for s in sets_of_items]
+    flat = [it for s in sets for it in s]
+    owner = [k for k, s in enumerate(sets) for _ in s]
+    errs, todo, gpu_items = _host_checks(spec, flat)
+    out = [None] * len(sets)
+    for k, e in zip(owner, errs):
+        if e is not None and out[k] is None:
+            out[k] = e
+    live = [k for k in range(len(sets)) if out[k] is None]
+    by_set = {k: [] for k in live}
+    for i, item in zip(todo, gpu_items):
+        if owner[i] in by_set:
+            by_set[owner[i]].append(item)
+    if any(by_set[k] for k in live):
+        for k, ok in zip(live, tbls.verify_sets_batch([by_set[k] for k in live], engine)):
+            if not ok:
+                out[k] = SigningError(SET_FAILED)
     return out
 
 

@@ -215,6 +215,32 @@ def verify_batch(items, engine=None):
     return out
 
 
+def verify_sets_batch(sets, engine=None):
+    """sets: list of lists of (pk, msg, sig).  Returns True per set whose
+    every item verifies, else False -- all or nothing, the meaning of a
+    receive path that drops a whole set on its first failing item (reference
+    core/parsigex/parsigex.go:101-107).  One set launch (tbg_submit_sets): a
+    failed set is not narrowed to its bad item, and a set with an item that
+    does not decode (SS_ERROR) is False too, since it is dropped either way.
+    An empty set is True."""
+    sets = [list(s) for s in sets]
+    items = [it for s in sets for it in s]
+    if not items:
+        return [True] * len(sets)
+    e = _engine(engine)
+    pks = [_raw(pk, PublicKey) if pk is not None else None for pk, _, _ in items]
+    present = [p for p in pks if p is not None]
+    ids_present = iter(_pk_cache.ids_for(e, present))
+    pk_ids = [next(ids_present) if p is not None else eng.NO_PUBKEY for p in pks]
+    msgs = [bytes(m) for _, m, _ in items]
+    sigs = b"".join(_raw(s, Signature) for _, _, s in items)
+    n = len(items)
+    set_first = np.concatenate([[0], np.cumsum([len(s) for s in sets])])
+    res = e.run_sets(set_first, np.arange(n + 1), sigs, np.zeros(n, np.uint8), msgs=msgs, duty_msg=np.arange(n),
+                     pubkey_ids=pk_ids)
+    return [st == eng.SS_VALID for st in res.set_status.tolist()]
+
+
 def _duty_arrays(duties, with_msg):
     duty_first = [0]
     sigs, ids, msgs, thr, pk_keys = [], [], [], [], []

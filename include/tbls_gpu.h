@@ -59,6 +59,13 @@ extern "C" {
 #define TBG_DS_DECODE (-25)              /* a partial failed to decode (SigFromCore error)    */
 #define TBG_DS_NOT_AGGREGATED 1          /* TBG_OP_VERIFY: no aggregate produced              */
 
+/* ---- per-set status (int32, tbg_submit_sets) ------------------------------
+ * ERROR < INVALID < VALID, so a set's status is the minimum over its members
+ * (composed on the device by atomicMin); distinct from every TBG_DS_* code. */
+#define TBG_SS_ERROR 30    /* a member has a negative TBG_PS_* code (decode, subgroup, identity, pubkey) */
+#define TBG_SS_INVALID 31  /* no negative code, and some member's pairing check is false (or its H(m) unusable) */
+#define TBG_SS_VALID 32    /* every member is TBG_PS_VALID (an empty set, a set of empty duties: VALID) */
+
 #define TBG_NO_PUBKEY 0xFFFFFFFFu        /* pubkey_ids[] entry: identifier not in the TSS     */
 
 typedef enum {
@@ -225,6 +232,37 @@ int tbg_submit_group(tbg_ctx* ctx, const tbg_batch* const* batches, uint32_t n_b
  * context lock, so other threads keep submitting / polling meanwhile. */
 int tbg_collect(tbg_ctx* ctx, tbg_ticket ticket, int32_t* partial_status, int32_t* duty_status,
                 uint8_t* agg96, int block);
+
+/* All-or-nothing verification of SETS of duties (parsigex drops a peer's whole
+ * set on its first failing partial, core/parsigex/parsigex.go:101-107): set k
+ * owns duties [set_first[k], set_first[k+1]) of `batch` (op TBG_OP_VERIFY), and
+ * set_status[k] is TBG_SS_VALID iff TBG_OP_VERIFY would give every partial of
+ * the set TBG_PS_VALID -- TBG_SS_ERROR / TBG_SS_INVALID otherwise, by the rule
+ * at the TBG_SS_* codes.  A failed set is NOT narrowed to its bad partial: a
+ * set launch runs none of the levels 1g / 1.5 / 1.5b / 2b, and level 3 only for
+ * what needs the exact check anyway (a degenerate combination, every partial
+ * under TBG_VERIFY_EACH).  Level-1 groups never straddle a set: every set
+ * starts on a multiple of the group size G in the device batch (empty padding
+ * duties), and an unconfigured G shrinks (16 -> 8 -> 4) while the padding
+ * would pass 1/8 of the duties.  A false accept stays <= 2^-64 per check.
+ * TBG_E_INVALID_ARG unless set_first[0] == 0, set_first is non-decreasing,
+ * set_first[n_sets] == n_duties and op == TBG_OP_VERIFY.
+ * partial_status (optional): negative codes exact; a candidate is
+ * TBG_PS_VALID if its set is TBG_SS_VALID, else TBG_PS_NOT_VERIFIED.
+ * A set ticket works with tbg_poll, tbg_replay, tbg_replay_profile,
+ * tbg_fetch_fallback (0 for the levels 1g, 1.5, 1.5b, 2b), _level0, _subgroup,
+ * _shape, _stats and tbg_slot_bytes; tbg_collect / tbg_fetch of a set ticket
+ * and tbg_collect_sets / tbg_fetch_sets of a plain one return TBG_E_TICKET.
+ * The adaptive policies count every candidate of a failed group as invalid
+ * (an upper bound of the invalid share).
+ * Out of scope: tbg_multi_* for sets (the shard cut would have to fall on set
+ * boundaries) and a tbg_submit_group of set batches (a caller coalesces peers
+ * by passing many sets in one call). */
+int tbg_submit_sets(tbg_ctx* ctx, const tbg_batch* batch, const uint32_t* set_first, uint32_t n_sets,
+                    tbg_ticket* ticket);
+int tbg_collect_sets(tbg_ctx* ctx, tbg_ticket ticket, int32_t* set_status, int32_t* partial_status, int block);
+/* After a tbg_replay of a collected set ticket: the slot's current outputs. */
+int tbg_fetch_sets(tbg_ctx* ctx, tbg_ticket ticket, int32_t* set_status, int32_t* partial_status);
 
 /* Non-consuming readiness check: TBG_OK when finished, TBG_E_PENDING, or an
  * error code (unknown ticket / device failure). */
