@@ -157,6 +157,42 @@ def verify_multi_signature(agg_pk48: bytes, msg: bytes, agg_sig96: bytes, engine
     return r
 
 
+def create_cluster_tss(secrets, t: int, n: int, rng, engine=None):
+    """getTSSShares of `charon create cluster` (cmd/createcluster.go:250-270):
+    every validator secret split t-of-n and its TSS.  One split on the host
+    (integers), ONE sk_to_pk launch for every commitment and every pubshare
+    (the shares are at hand here, so pubshare i is sk_to_pk(f(i))) and ONE
+    key_from_bytes_batch that validates the pubshares and leaves them
+    resident for the verifies that follow, instead of a SplitSecret + NewTSS
+    pair per validator.  Returns (list of TSS, list of share lists).  Host
+    integers and the test-only tbg_sk_to_pk: not side-channel safe, not for
+    production keys (tbls.split_secret)."""
+    e = tbls._engine(engine)
+    splits, polys = [], []
+    for s in secrets:
+        shares, poly = tbls._split_host(s, t, n, rng)
+        splits.append(shares)
+        polys.append(poly)
+    if not splits:
+        return [], []
+    scalars = [c for p in polys for c in p] + [s.value for sh in splits for s in sh]
+    pks = [bytes(k) for k in e.sk_to_pk(b"".join(tbls._sk32(v) for v in scalars))]
+    nd = len(polys)
+    commits, shares48 = pks[:nd * t], pks[nd * t:]
+    keys = tbls.key_from_bytes_batch(shares48, e)
+    dvs = []
+    for d in range(nd):
+        pub = {}
+        for i in range(n):
+            k = keys[d * n + i]
+            if isinstance(k, Exception):
+                raise tbls.TblsError(str(k).replace("unmarshal pubkey", "unmarshal pubshare"))
+            pub[i + 1] = k
+        c = commits[d * t:(d + 1) * t]
+        dvs.append(tbls.TSS(pub, n, t, tbls.PublicKey(c[0]), tuple(c)))
+    return dvs, splits
+
+
 def _lock_bytes(v) -> bytes:
     """Lock JSON byte fields: 0x-hex (v1.2+) or base64 (v1.0 / v1.1)."""
     if v is None:

@@ -8,6 +8,8 @@ parity test reads like ``tbls/tss_test.go``:
   aggregate(partial_sigs) -> Signature                 tss.go:142-149
   verify_and_aggregate(tss, partial_sigs, msg)         tss.go:153-187
   TSS(pubshares, num_shares, threshold, public_key)    tss.go:62-116
+  split_secret / combine_shares / generate_tss         tss.go:256-290, 220-253, 120-139
+  sign / partial_sign (test-only, not side-channel safe)  tss.go:200-217
 
 plus the batch entry points the batch-aware call sites use:
 
@@ -73,6 +75,7 @@ class TSS:
     num_shares: int
     threshold: int
     public_key: PublicKey | None = None
+    commitments: tuple = ()  # the Feldman commitments [a_j] g1 (48 bytes each) when built by generate_tss
 
     def public_share(self, share_idx: int):
         return self.pubshares.get(share_idx)
@@ -330,3 +333,122 @@ def verify_and_aggregate(tss: TSS, partial_sigs, msg: bytes, engine=None):
     if isinstance(r, Exception):
         raise r
     return r
+
+
+# ------------------------------------------------- the key side of tss.go (test clusters)
+R = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001  # the group order
+
+
+@dataclass(frozen=True)
+class SecretKeyShare:
+    """bls_sig.SecretKeyShare{identifier byte; value}: f(identifier) mod r."""
+    identifier: int
+    value: int
+
+    def __post_init__(self):
+        if not 1 <= self.identifier <= 255:
+            raise TblsError("share identifier must be 1..255")
+
+
+def _sk32(v: int) -> bytes:
+    return (int(v) % R).to_bytes(32, "big")
+
+
+def split_secret(secret: int, t: int, n: int, rng, engine=None):
+    """tbls.SplitSecret (tss.go:256-290): n shares f(1..n) of f(x) = secret +
+    a_1 x + ... + a_(t-1) x^(t-1) mod r, the a_j drawn from ``rng``
+    (``randrange``), and the t Feldman commitments [a_j] g1 (48 bytes each,
+    through Engine.sk_to_pk).  Host integers: NOT side-channel safe, and the
+    engine's sk_to_pk is the test-only double-and-add of tbg_sk_to_pk -- not
+    for production keys."""
+    shares, poly = _split_host(secret, t, n, rng)
+    commits = _engine(engine).sk_to_pk(b"".join(_sk32(c) for c in poly))
+    return shares, [bytes(c) for c in commits]
+
+
+def _split_host(secret: int, t: int, n: int, rng):
+    """The integer half of split_secret: (shares, polynomial coefficients)."""
+    if not (2 <= t <= n <= 255):
+        raise TblsError("new Feldman VSS: need 2 <= t <= n <= 255")
+    secret = int(secret) % R
+    if secret == 0:
+        raise TblsError("convert to scaler: zero secret")
+    poly = [secret] + [rng.randrange(1, R) for _ in range(t - 1)]
+    shares = []
+    for i in range(1, n + 1):
+        acc = 0
+        for c in reversed(poly):
+            acc = (acc * i + c) % R
+        shares.append(SecretKeyShare(i, acc))
+    return shares, poly
+
+
+def tss_from_shares(shares, commits, engine=None) -> TSS:
+    """The TSS of a split whose scalar shares are at hand: pubshare i is
+    sk_to_pk(f(i)) (what NewTSS's sum over the commitments evaluates to), the
+    group key is C_0 and the threshold is the number of commitments.  Only
+    for callers that hold the shares (GenerateTSS, create cluster): deriving
+    the pubshares from the commitments alone (tbls.NewTSS proper) is not
+    implemented.  Test-only scalar multiplication, see split_secret."""
+    shares = list(shares)
+    commits = [bytes(c) for c in commits]
+    pks = _engine(engine).sk_to_pk(b"".join(_sk32(s.value) for s in shares))
+    ident = bytes([0xC0]) + bytes(47)
+    if commits[0] == ident:
+        raise TblsError("unmarshal pubkey: " + _PK_ERRORS[1])
+    pub = {}
+    for s, pk in zip(shares, pks):
+        if bytes(pk) == ident:
+            raise TblsError("unmarshal pubshare: " + _PK_ERRORS[1])
+        pub[s.identifier] = PublicKey(bytes(pk))
+    return TSS(pub, len(shares), len(commits), PublicKey(commits[0]), tuple(commits))
+
+
+def generate_tss(t: int, n: int, rng, engine=None):
+    """tbls.GenerateTSS (tss.go:120-139): a random secret split t-of-n and its
+    TSS.  Returns (TSS, shares, secret); the secret is returned for the parity
+    tests (the reference discards it).  Test clusters only: see split_secret."""
+    secret = rng.randrange(1, R)
+    try:
+        shares, commits = split_secret(secret, t, n, rng, engine)
+    except TblsError as err:
+        raise TblsError("generate secret shares: " + str(err))
+    return tss_from_shares(shares, commits, engine), shares, secret
+
+
+def combine_shares(shares, t: int, n: int) -> int:
+    """tbls.CombineShares (tss.go:220-253): the secret from at least t shares,
+    Lagrange interpolation at 0 mod r over ALL shares given.  Host integers,
+    not side-channel safe: not for production keys."""
+    shares = list(shares)
+    if not (2 <= t <= n <= 255):
+        raise TblsError("new Feldman VSS: need 2 <= t <= n <= 255")
+    if len(shares) < t:
+        raise TblsError("combine shares: fewer shares than the threshold")
+    ids = [s.identifier for s in shares]
+    if len(set(ids)) != len(ids):
+        raise TblsError("combine shares: duplicate share identifier")
+    if any(i > n for i in ids):
+        raise TblsError("combine shares: invalid share identifier")
+    acc = 0
+    for s in shares:
+        num = den = 1
+        for j in ids:
+            if j != s.identifier:
+                num = num * j % R
+                den = den * (j - s.identifier) % R
+        acc = (acc + s.value * num * pow(den, R - 2, R)) % R
+    return acc
+
+
+def sign(secret: int, msg: bytes, engine=None) -> Signature:
+    """tbls.Sign (tss.go:210-217) over Engine.sign.  TEST-ONLY like tbg_sign:
+    a plain double-and-add whose timing depends on the key -- not side-channel
+    safe, never for a production validator key."""
+    return Signature(bytes(_engine(engine).sign(_sk32(secret), [bytes(msg)], [0])[0]))
+
+
+def partial_sign(share: SecretKeyShare, msg: bytes, engine=None) -> PartialSignature:
+    """tbls.PartialSign (tss.go:200-207) over Engine.sign.  TEST-ONLY like
+    tbg_sign: not side-channel safe, never for a production key share."""
+    return PartialSignature(share.identifier, sign(share.value, msg, engine))
