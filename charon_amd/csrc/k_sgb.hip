@@ -33,7 +33,7 @@
 #endif
 #include "tbls_launch.h"
 #include "bls_rlc.h"
-#include "bls_pair.h"
+#include "bls_sgb.h"
 
 namespace tbg {
 
@@ -138,8 +138,9 @@ __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_bucket(DevBatch B, uint32_t n
   px_store(B.sgb_part[w], acc);
 }
 
-// A failed group: its members are tested alone, and the fused level 0, whose
-// S is built from the groups' sums (k_msm.hip), is void for the launch.
+// A failed group (k_sgb_test alone decides): its members are tested alone, and
+// the fused level 0, whose S is built from the groups' sums (k_msm.hip), is
+// void for the launch.
 __device__ __forceinline__ void sgb_fail(const DevBatch& B, uint32_t g) {
   B.sgb_bad[g] = 1u;
   if (l0_fused(B)) B.counters[CNT_L0_BAD] = 1u;
@@ -149,39 +150,45 @@ __device__ __forceinline__ void sgb_fail(const DevBatch& B, uint32_t g) {
 // its first slice, so the running sums below are 2 x SGB_V additions deep
 // instead of (SGB_SPLIT + 1) x SGB_V (a latency-bound kernel: few waves,
 // each one serial chain).  The additions skip the doubling case (bls_pair.h
-// jac_add_x: fewer live values than the complete formulas): two equal
-// partial sums -- which random digits make negligible -- fail the group,
-// whose members are then tested one by one.
+// jac_add_x: fewer live values than the complete formulas).  Two equal
+// operands are no sign of a bad signature: a short last group's empty
+// buckets make the running sums meet them almost surely, and replayed
+// signatures make equal slice and bucket sums.  The pair that met them redoes
+// its one sum with the complete formulas, out of line (bls_sgb.h); only
+// k_sgb_test fails a group.
+__device__ __noinline__ Jac<Fp2x> sgb_fold_complete(const G2J* part, uint32_t S) {
+  bool unused = false;
+  return sgb_fold_g<Fp2x, false>([&](uint32_t sl) { return px_load(part[sl]); }, S, unused);
+}
+
 __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_fold(DevBatch B, uint32_t n_sg) {
   const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;  // both lanes of a pair take the same branches
   if (w >= n_sg * SGB_BUCKETS) return;
   const uint32_t S = B.sgb_split;
   G2J* part = B.sgb_part + (size_t)w * S;
-  Jac<Fp2x> acc = px_load(part[0]);
   bool exc = false;
-#pragma unroll 1
-  for (uint32_t sl = 1; sl < S; ++sl) acc = jac_add_x(acc, px_load(part[sl]), exc);
-  if (pair_all(!exc)) px_store(part[0], acc);
-  else if (pair_par() == 0) sgb_fail(B, w / SGB_BUCKETS);
+  Jac<Fp2x> acc = sgb_fold_g<Fp2x, true>([&](uint32_t sl) { return px_load(part[sl]); }, S, exc);
+  if (!pair_all(!exc)) acc = sgb_fold_complete(part, S);  // (pair-uniform)
+  px_store(part[0], acc);
 }
 
 // one lane pair per (group, combination): Q_k = sum_v v B_v by running sums
 // from v = 6 down over the folded buckets, stored over the combination's
 // first bucket (only this pair reads those buckets)
+__device__ __noinline__ Jac<Fp2x> sgb_combine_complete(const G2J* part, uint32_t S) {
+  bool unused = false;
+  return sgb_running_sums_g<Fp2x, false>([&](uint32_t v) { return px_load(part[(size_t)v * S]); }, SGB_V, unused);
+}
+
 __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_combine(DevBatch B, uint32_t n_sg) {
   const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;  // both lanes of a pair take the same branches
   if (w >= n_sg * SGB_K) return;
   const uint32_t g = w / SGB_K, k = w % SGB_K, S = B.sgb_split;
   G2J* part = B.sgb_part + ((size_t)SGB_BUCKETS * g + (size_t)SGB_V * k) * S;
-  Jac<Fp2x> run = jac_inf<Fp2x>(), q = run;
   bool exc = false;
-#pragma unroll 1
-  for (int v = (int)SGB_V; v >= 1; --v) {
-    run = jac_add_x(run, px_load(part[(size_t)(v - 1) * S]), exc);
-    q = jac_add_x(q, run, exc);
-  }
-  if (pair_all(!exc)) px_store(part[0], q);
-  else if (pair_par() == 0) sgb_fail(B, g);
+  Jac<Fp2x> q = sgb_running_sums_g<Fp2x, true>([&](uint32_t v) { return px_load(part[(size_t)v * S]); }, SGB_V, exc);
+  if (!pair_all(!exc)) q = sgb_combine_complete(part, S);  // (pair-uniform)
+  px_store(part[0], q);
 }
 
 // one lane pair per (group, combination): psi(Q) == [x] Q; a failure (or the

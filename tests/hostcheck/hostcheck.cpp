@@ -1131,6 +1131,7 @@ int hc_row_lines(const uint8_t* q192) {
 }
 
 #include "../../charon_amd/csrc/bls_rlc.h"
+#include "../../charon_amd/csrc/bls_sgb.h"
 extern "C" {
 // The batched subgroup test's coefficients of partial i (sgb_digits).
 void hc_sgb_digits(const uint32_t* seed8, uint32_t i, int32_t* out18) {
@@ -1142,39 +1143,67 @@ void hc_sgb_digits(const uint32_t* seed8, uint32_t i, int32_t* out18) {
 }
 // k_sgb.hip's test of one group, lane pairs emulated (Fp2p): the n 96-byte
 // signatures of partials i0 .. i0 + n - 1 decoded WITHOUT the subgroup check
-// (a decode failure leaves the partial out, as in the kernels), the 18
-// bucket sums of each combination, Q_k by running sums, psi(Q_k) == [x] Q_k.
-// Returns the bit mask of the combinations that failed (-1: bad argument).
-int hc_sgb_group(const uint8_t* sigs96, int n, const uint32_t* seed8, uint32_t i0) {
-  if (n < 0 || n > 512) return -1;
+// (a decode failure leaves the partial out, as in the kernels); per
+// combination the six buckets' `split` slice sums (k_sgb_bucket: slice sl
+// holds entries [n sl / split, n (sl + 1) / split) of the bucket), their fold
+// and the running sums by the kernels' own templates (bls_sgb.h: additions
+// without the doubling branch, a sum that met equal operands redone with the
+// complete formulas), then psi(Q_k) == [x] Q_k as k_sgb_test.
+// Returns the bit mask of the combinations that failed (-1: bad argument);
+// *n_redo (may be null) counts the sums that were redone.  redo = 0 is the
+// control the tests use to show that a case reaches the exceptional path: a
+// sum that met equal operands then fails its combination, which is what the
+// kernels did before they redid such sums.
+int hc_sgb_group_ex(const uint8_t* sigs96, int n, const uint32_t* seed8, uint32_t i0, uint32_t split, int redo,
+                    int* n_redo) {
+  if (n < 0 || n > 512 || split < 1 || split > 8) return -1;
   uint32_t seed[8];
   for (int k = 0; k < 8; ++k) seed[k] = seed8[k];
   static G2A pts[512];
   static bool ok[512];
+  static uint32_t ent[6][512];
   for (int i = 0; i < n; ++i) ok[i] = g2_decompress_t<false, false>(sigs96 + 96 * i, pts[i]) == DEC_OK;
-  int mask = 0;
+  int mask = 0, redone = 0;
   for (int k = 0; k < 18; ++k) {
-    Jac<Fp2p> bucket[6];
-    for (auto& b : bucket) b = jac_inf<Fp2p>();
+    uint32_t cnt[6] = {0, 0, 0, 0, 0, 0};
     for (int i = 0; i < n; ++i) {
       if (!ok[i]) continue;
       int32_t c[18];
       sgb_digits(seed, i0 + (uint32_t)i, c);
       if (!c[k]) continue;
-      Aff<Fp2p> p{pp_from(pts[i].x), f_reduce(pp_from(pts[i].y))};
-      if (c[k] < 0) p.y = f_reduce(f_neg(p.y));
-      bucket[(c[k] < 0 ? -c[k] : c[k]) - 1] = jac_add_aff_in(bucket[(c[k] < 0 ? -c[k] : c[k]) - 1], p);
+      const uint32_t v = (uint32_t)(c[k] < 0 ? -c[k] : c[k]) - 1;
+      ent[v][cnt[v]++] = ((uint32_t)i << 1) | (c[k] < 0 ? 1u : 0u);
     }
-    Jac<Fp2p> run = jac_inf<Fp2p>(), q = run;
-    for (int v = 6; v >= 1; --v) {
-      run = jac_add_in<Fp2p, true>(run, bucket[v - 1]);
-      q = jac_add_in<Fp2p, true>(q, run);
-    }
-    bool pass = true;
-    if (!jac_is_inf(q)) {
+    bool failed = false;
+    Jac<Fp2p> bucket[6];
+    for (uint32_t v = 0; v < 6; ++v) {
+      Jac<Fp2p> part[8];
+      for (uint32_t sl = 0; sl < split; ++sl) {
+        Jac<Fp2p> acc = jac_inf<Fp2p>();
+        for (uint32_t e = (cnt[v] * sl) / split; e < (cnt[v] * (sl + 1)) / split; ++e) {
+          const G2A& s = pts[ent[v][e] >> 1];
+          Aff<Fp2p> p{pp_from(s.x), f_reduce(pp_from(s.y))};
+          if (ent[v][e] & 1u) p.y = f_reduce(f_neg(p.y));
+          acc = jac_add_aff_in(acc, p);
+        }
+        part[sl] = acc;
+      }
       bool exc = false;
-      const Jac<Fp2p> m = jac_mul_xabs_x(q, exc);
-      if (exc || jac_is_inf(m)) {
+      auto slice = [&](uint32_t sl) { return part[sl]; };
+      bucket[v] = sgb_fold_g<Fp2p, true>(slice, split, exc);
+      if (exc && redo) { bucket[v] = sgb_fold_g<Fp2p, false>(slice, split, exc); ++redone; }
+      else if (exc) failed = true;
+    }
+    bool exc = false;
+    auto ld = [&](uint32_t v) { return bucket[v]; };
+    Jac<Fp2p> q = sgb_running_sums_g<Fp2p, true>(ld, 6, exc);
+    if (exc && redo) { q = sgb_running_sums_g<Fp2p, false>(ld, 6, exc); ++redone; }
+    else if (exc) failed = true;
+    bool pass = !failed;
+    if (pass && !jac_is_inf(q)) {
+      bool xexc = false;
+      const Jac<Fp2p> m = jac_mul_xabs_x(q, xexc);
+      if (xexc || jac_is_inf(m)) {
         pass = false;
       } else {
         const Jac<Fp2p> ps = g2_psi_g(q);
@@ -1185,7 +1214,12 @@ int hc_sgb_group(const uint8_t* sigs96, int n, const uint32_t* seed8, uint32_t i
     }
     if (!pass) mask |= 1 << k;
   }
+  if (n_redo) *n_redo = redone;
   return mask;
+}
+// (one slice per bucket, sums redone as in the kernels)
+int hc_sgb_group(const uint8_t* sigs96, int n, const uint32_t* seed8, uint32_t i0) {
+  return hc_sgb_group_ex(sigs96, n, seed8, i0, 1, 1, nullptr);
 }
 }
 
@@ -1246,5 +1280,45 @@ void hc_g2_lines_raw(const uint32_t* q, uint32_t* out) {
   const G2A Q{{raw_in(q), raw_in(q + NL)}, {raw_in(q + 2 * NL), raw_in(q + 3 * NL)}};
   const Fp nx = fp_reduce(fp_neg(fp_from_const(G1_X))), y = fp_from_const(G1_NEG_Y);
   g2_lines(Q, nx, y, out);
+}
+// The lane-pair G2 group law on raw limbs (an Fp2 is c0, c1: 2 x 14 words; an
+// affine point 4 x 14; a Jacobian point 6 x 14), lane pairs emulated (Fp2p):
+// the operation codes of tests/devcheck/devcheck_g2.hip.  out: one Jacobian
+// point (84 words; in_subgroup_aff writes none); *flag: bit 0 `exc`, bit 1 the
+// subgroup test's verdict.  -1 for an unknown op.
+static Fp2p raw_f2(const uint32_t* l) { return {raw_in(l), raw_in(l + NL)}; }
+static Jac<Fp2p> raw_jac(const uint32_t* l) { return {raw_f2(l), raw_f2(l + 2 * NL), raw_f2(l + 4 * NL)}; }
+static Aff<Fp2p> raw_aff(const uint32_t* l) { return {raw_f2(l), raw_f2(l + 2 * NL)}; }
+int hc_g2_op_raw(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t* flag) {
+  bool exc = false, verdict = false;
+  Jac<Fp2p> r = jac_inf<Fp2p>();
+  auto six = [&](uint32_t v) { return raw_jac(a + 6 * NL * v); };
+  switch (op) {
+    case 0: r = jac_add_x(raw_jac(a), raw_jac(b), exc); break;
+    case 1: r = jac_add_aff_x(raw_jac(a), raw_aff(b), exc); break;
+    case 2: r = jac_dbl_lo(raw_jac(a)); break;
+    case 3: r = jac_add_in<Fp2p, true>(raw_jac(a), raw_jac(b)); break;
+    case 4: r = jac_add_aff_in(raw_jac(a), raw_aff(b)); break;
+    case 5: r = g2_psi_g(raw_jac(a)); break;
+    case 6: r = jac_mul_xabs_x(raw_jac(a), exc); break;
+    case 7: r = jac_mul_xabs_aff_x(raw_aff(a), exc); break;
+    case 8: verdict = g2_in_subgroup_aff_g(raw_aff(a), exc); break;
+    case 9: r = g2_clear_cofactor_g(raw_jac(a), exc); break;
+    case 10: r = sgb_running_sums_g<Fp2p, true>(six, 6, exc); break;
+    case 11: r = sgb_running_sums_g<Fp2p, false>(six, 6, exc); break;
+    case 12: r = sgb_fold_g<Fp2p, true>(six, 4, exc); break;
+    case 13: r = sgb_fold_g<Fp2p, false>(six, 4, exc); break;
+    default: return -1;
+  }
+  *flag = (exc ? 1u : 0u) | (verdict ? 2u : 0u);
+  if (op != 8) {
+    const Fp2p* c[3] = {&r.X, &r.Y, &r.Z};
+    for (int k = 0; k < 3; ++k)
+      for (int i = 0; i < NL; ++i) {
+        out[(2 * k) * NL + i] = c[k]->c0.l[i];
+        out[(2 * k + 1) * NL + i] = c[k]->c1.l[i];
+      }
+  }
+  return 0;
 }
 }

@@ -210,3 +210,99 @@ def test_fp12_flag_and_line_checkers_reject_one_off():
     for j in (0, 13, 14 * 6 * 67 + 5, len(ref) - 1):
         for w in _perturbed(ref, [j]):
             assert eo.check_lines(w, ref) is not None
+
+
+# ---------------------------------------------------------------------------
+# the lane-pair G2 group law (tests/edge_points.py; the GPU run:
+# test_gpu_devcheck_g2.py)
+from tests import edge_points as ep  # noqa: E402
+
+
+def host_g2(op, aw, bw):
+    a = (ctypes.c_uint32 * len(aw))(*aw)
+    b = (ctypes.c_uint32 * len(bw))(*bw) if bw is not None else None
+    out = (ctypes.c_uint32 * 84)(*([eo.SENTINEL] * 84))
+    flag = ctypes.c_uint32(eo.SENTINEL)
+    assert lib().hc_g2_op_raw(ep.OPS.index(op), a, b, out, ctypes.byref(flag)) == 0
+    return list(out), flag.value
+
+
+@pytest.mark.parametrize("op", ep.OPS)
+def test_g2_lists_on_host(op):
+    cases = ep.cases()[op]
+    assert len(cases) >= 8
+    for i, (aw, bw, expect) in enumerate(cases):
+        words, flag = host_g2(op, aw, bw)
+        err = ep.check(op, words, flag, expect)
+        assert err is None, (op, i, err)
+        if op == "in_subgroup_aff":
+            assert words == [eo.SENTINEL] * 84
+
+
+def test_g2_lists_hold_the_directed_cases():
+    """The lists reach what they are for, and the restated schedules agree
+    with the oracle where it has the operation."""
+    c, b = ep.cases(), ep.bank()
+    for op in ("add_x", "add_aff_x"):
+        excs = [e[1] for _, _, e in c[op]]
+        infs = [e[0] is None and not e[1] for _, _, e in c[op]]
+        assert sum(excs) >= 8 and sum(infs) >= 8 and len(excs) > 32 and len(excs) % 32 != 0
+        # neighbouring pairs differ in kind: no run of three equal outcomes
+        kinds = [(e[1], e[0] is None) for _, _, e in c[op]]
+        assert all(len({kinds[i], kinds[i + 1], kinds[i + 2]}) > 1 for i in range(30))
+    # every pattern of empty buckets; many of them add the running sum to itself
+    sums = c["sgb_sums"]
+    assert len(sums) >= 64 + 4
+    n_exc = sum(e[1] for _, _, e in sums[:64])
+    assert 20 <= n_exc < 64
+    assert sums[0][2] == (None, False, False)                       # all empty
+    assert sums[1][2] == (b["g"][0], False, False)                  # only bucket 1
+    assert sums[2][2][1] is True                                    # only bucket 2: run + run
+    assert sums[64][2][1] is True                                   # all buckets equal
+    for (_, _, fast), (_, _, full) in zip(sums, c["sgb_sums_complete"]):
+        assert fast[1] or fast[0] == full[0]                        # without exc the two agree
+    assert any(e[1] for _, _, e in c["sgb_fold"]) and not all(e[1] for _, _, e in c["sgb_fold"])
+    # the oracle's own decisions
+    g0 = b["g"][0]
+    assert ep.psi(g0) == bls.g2_mul(g0, bls.X % bls.R)              # psi acts as [x] on G2
+    verdicts = [e[2] for _, _, e in c["in_subgroup_aff"]]
+    pts = [g0, b["tor"], b["ns"], b["g"][1], b["t13"], b["t23"], b["g"][2], b["g"][3]]
+    assert len(verdicts) == len(pts)
+    for v, p, (_, _, e) in zip(verdicts, pts, c["in_subgroup_aff"]):
+        assert e[1] or v == bls.g2_in_subgroup(p)
+    assert verdicts.count(True) == 4
+    for (_, _, e), p in zip(c["clear_cofactor"], [g0, b["tor"], b["ns"]]):
+        if not e[1]:
+            assert e[0] == bls.clear_cofactor_g2(p)
+    assert c["clear_cofactor"][2][2][1] is False and c["clear_cofactor"][2][2][0] is not None  # E2 outside G2
+    assert bls.g2_in_subgroup(c["clear_cofactor"][2][2][0])
+    for (_, _, e), p in zip(c["mul_xabs_x"], pts[:3]):
+        if not e[1]:
+            assert e[0] == bls.g2_mul_raw(p, bls.X_ABS)
+
+
+def test_g2_checker_rejects_one_limb_off():
+    for op in ("add_x", "add_in", "dbl_lo", "psi", "sgb_sums_complete"):
+        done = 0
+        for aw, bw, expect in ep.cases()[op]:
+            if expect[0] is None:
+                continue
+            words, flag = host_g2(op, aw, bw)
+            assert ep.check(op, words, flag, expect) is None
+            assert ep.check(op, words, flag ^ 1, expect) is not None
+            for w in _perturbed(words, range(0, 84, 5)):
+                assert ep.check(op, w, flag, expect) is not None, (op, w)
+            done += 1
+            if done == 3:
+                break
+        assert done == 3
+    # infinity is Z == 0 mod p whatever X and Y hold; a non-zero Z is not infinity
+    aw, bw, expect = next(c for c in ep.cases()["add_x"] if c[2][0] is None and not c[2][1])
+    words, flag = host_g2("add_x", aw, bw)
+    assert ep.check("add_x", words, flag, expect) is None
+    words[5 * 14] += 1
+    assert ep.check("add_x", words, flag, expect) is not None
+    aw, bw, expect = ep.cases()["in_subgroup_aff"][0]
+    words, flag = host_g2("in_subgroup_aff", aw, bw)
+    assert ep.check("in_subgroup_aff", words, flag, expect) is None
+    assert ep.check("in_subgroup_aff", words, flag ^ 2, expect) is not None

@@ -211,3 +211,93 @@ def test_smaller_groups_after_non_subgroup_history():
         assert FUSED_KERNELS <= ks and "k_msm_bucket_part" not in ks
     finally:
         e.close()
+
+
+# ---- the group law's exceptional cases inside the batched test's sums ------
+# k_sgb_fold / k_sgb_combine add without a doubling branch and redo a sum that
+# met two equal operands with the complete formulas (bls_sgb.h).  Equal
+# operands are certain in a short last group (an empty bucket below the
+# highest non-empty one adds run to q == run) and in groups of replayed
+# signatures (equal slice and bucket sums); neither may fail a group or void
+# level 0.  2,049 .. 2,056 partials: two full groups and a tail of 1, 4, 8,
+# the smallest batches that run the batched test.
+
+@pytest.fixture(scope="module")
+def sums_engine():
+    """A context of its own with ctx's settings: the group size follows the
+    non-subgroup share of the batches a context has collected, and these tests
+    state it (1,024: a clean history)."""
+    from charon_amd import engine as eng
+    e = eng.Engine(0, slots=1, subgroup_batch=eng.SGB_ON, rlc_batch=eng.RLC_L0_ON)
+    yield e
+    e.close()
+
+
+def short_tail_batch(e, n_dv, t, n, seed):
+    from tools.workload import make_batch
+    b = make_batch(e, n_dv, t, n, seed=seed)
+    assert 2048 < len(b.sigs) <= 2048 + 16
+    return b
+
+
+@pytest.mark.parametrize("n_dv,t,n,tail", [(683, 2, 3, 1), (513, 3, 4, 4), (514, 3, 4, 8)],
+                         ids=["tail1", "tail4", "tail8"])
+def test_clean_short_tail_group_passes(sums_engine, n_dv, t, n, tail):
+    from charon_amd import engine as eng
+    from tests.test_gpu_fullsize import assert_same, oracle_run
+    e = sums_engine
+    b = short_tail_batch(e, n_dv, t, n, seed=7300 + tail)
+    assert len(b.sigs) == 2048 + tail
+    res, tk = run(e, b)
+    print("short tail", tail, "subgroup", e.subgroup(tk), "level0", e.level0(tk))
+    assert_same(res, oracle_run(b))
+    assert e.level0(tk) == eng.L0_PASSED
+    assert e.subgroup(tk) == {"groups": 3, "failed": 0, "group_size": 1024}
+    assert (res.partial_status == eng.PS_VALID).all() and np.array_equal(res.agg, b.group_sig)
+
+
+def test_replayed_duties_pass(sums_engine):
+    """8 distinct 3-of-4 duties tiled 64 times: 2,048 partials, every group
+    full of duplicates (32 signatures, 32 copies of each in a group of 1,024;
+    the context's history of non-subgroup partials may pick a smaller group
+    size, a multiple of 32 too)."""
+    import dataclasses
+    from charon_amd import engine as eng
+    from tests.test_gpu_fullsize import assert_same, oracle_run
+    from tools.workload import make_batch
+    e = sums_engine
+    base = make_batch(e, 8, T, N, seed=7373)
+    reps = 64
+    b = dataclasses.replace(
+        base, n_dv=8 * reps, duty_first=np.arange(8 * reps + 1, dtype=np.uint32) * N,
+        sigs=np.tile(base.sigs, (reps, 1)), identifiers=np.tile(base.identifiers, reps),
+        pubkey_ids=np.tile(base.pubkey_ids, reps), duty_msg=np.tile(base.duty_msg, reps),
+        threshold=np.tile(base.threshold, reps), group_sig=np.tile(base.group_sig, (reps, 1)))
+    assert len(b.sigs) == 2048
+    res, tk = run(e, b)
+    print("replayed subgroup", e.subgroup(tk), "level0", e.level0(tk))
+    assert_same(res, oracle_run(b))
+    sg = e.subgroup(tk)
+    assert sg["failed"] == 0 and sg["group_size"] % 32 == 0 and sg["groups"] == -(-2048 // sg["group_size"]), sg
+    assert e.level0(tk) == eng.L0_PASSED
+    assert (res.partial_status == eng.PS_VALID).all() and np.array_equal(res.agg, b.group_sig)
+
+
+def test_crafted_point_alone_in_the_tail_group_is_caught(sums_engine):
+    from charon_amd import engine as eng
+    from tests.test_gpu_fullsize import assert_same, oracle_run
+    e = sums_engine
+    b = short_tail_batch(e, 683, 2, 3, seed=7301)
+    with open(os.path.join(HERE, "golden", "sgb_points.json")) as f:
+        t13 = bytes.fromhex(json.load(f)["points"]["t13"][0])
+    pos = len(b.sigs) - 1
+    assert pos == 2048  # the sole member of the third group
+    sigs = np.array(b.sigs, copy=True)
+    sigs[pos] = np.frombuffer(t13, dtype=np.uint8)
+    res, tk = run(e, b, sigs=sigs)
+    print("crafted tail subgroup", e.subgroup(tk), "level0", e.level0(tk))
+    assert_same(res, oracle_run(variant(b, sigs=sigs)))
+    assert res.partial_status[pos] == eng.PS_ERR_SUBGROUP
+    assert np.flatnonzero(res.partial_status != eng.PS_VALID).tolist() == [pos]
+    assert e.subgroup(tk) == {"groups": 3, "failed": 1, "group_size": 1024}
+    assert e.level0(tk) == eng.L0_FAILED

@@ -142,6 +142,46 @@ def test_aggregate_golden(engine):
                 tbls.aggregate(d, engine)
 
 
+@pytest.mark.parametrize("order", ["forward", "reversed"])
+def test_aggregate_exceptional_golden(engine, order):
+    """The group law's exceptional cases inside the integer-form combination
+    (agg_exceptional.json, tests/golden/make_agg_exc_golden.py: an addition of
+    two equal points, which sends the duty to the reference path; cancellations
+    back to infinity mid-loop; identity sums; with D = 1 and D > 1), in ONE
+    batch, interleaved with the ordinary duties of aggregate_edges.json so that
+    a workgroup's batched inversion sees present, absent and handed-over pairs
+    side by side; status and 96-byte aggregate per duty against the oracle."""
+    from charon_amd import engine as eng, tbls
+    exc, edges = load("agg_exceptional.json"), load("aggregate_edges.json")
+    assert len(exc) == 10 and {v["expect"]["status"] for v in exc} == {"ok", "identity"}
+    vecs = []
+    for k in range(max(len(exc), len(edges))):
+        vecs += edges[k:k + 1] + exc[k:k + 1]
+    if order == "reversed":
+        vecs = vecs[::-1]
+    duties = [[tbls.PartialSignature(p["identifier"], tbls.Signature(bytes.fromhex(p["sig"]))) for p in v["partials"]]
+              for v in vecs]
+    duty_first = np.cumsum([0] + [len(d) for d in duties])
+    sigs = b"".join(p.signature.raw for d in duties for p in d)
+    ids = [p.identifier for d in duties for p in d]
+    res = engine.run(eng.OP_AGGREGATE, duty_first, sigs, ids)
+    for d, v in enumerate(vecs):
+        assert DS_NAMES[int(res.duty_status[d])] == v["expect"]["status"], (order, v["label"])
+        if v["expect"]["status"] == "ok":
+            assert bytes(res.agg[d]).hex() == v["expect"]["agg"], (order, v["label"])
+        else:
+            assert not np.asarray(res.agg[d]).any(), (order, v["label"])
+    # Go-API mirror
+    for d, v in zip(duties, vecs):
+        if "event" not in v:
+            continue
+        if v["expect"]["status"] == "ok":
+            assert tbls.aggregate(d, engine).raw.hex() == v["expect"]["agg"], v["label"]
+        else:
+            with pytest.raises(tbls.TblsError):
+                tbls.aggregate(d, engine)
+
+
 def test_engine_sign_matches_oracle(engine):
     """GPU test-vector generation (tbls.Sign) agrees with the oracle."""
     from oracle import bls12_381 as bls
