@@ -240,6 +240,7 @@ SIGNATURES = {
     "tbg_fetch_level0": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     "tbg_fetch_fallback": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     "tbg_fetch_subgroup": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "tbg_fetch_subgroup_schedule": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     "tbg_fetch_shape": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     "tbg_host_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
     "tbg_multi_host_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
@@ -293,7 +294,13 @@ def load() -> ctypes.CDLL:
             raise RuntimeError(f"{path} is missing: run __graft_entry__.build() (hipcc, gfx950)")
         lib = ctypes.CDLL(path)
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
+            fn = getattr(lib, name, None)
+            if fn is None:
+                # a variant built from an older tree (the parent arm of an A/B) may lack
+                # the newest entry points; the product library must have them all
+                if path == LIB_PATH:
+                    raise RuntimeError(f"{path} does not export {name}: rebuild it (__graft_entry__.build())")
+                continue
             fn.restype = res
             fn.argtypes = args
         _lib = lib

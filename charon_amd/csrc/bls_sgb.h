@@ -1,7 +1,8 @@
-// The batched subgroup test's sums over a group's bucket slices (k_sgb.hip),
-// written for any Fp2 representation so that the kernels (Fp2x, the lane
-// pair) and the host twin (Fp2p, tests/hostcheck hc_sgb_group) run the same
-// code.
+// The batched subgroup test's sums over a group's bucket (slice) sums
+// (k_sgb.hip), written for any Fp2 representation so that the kernels (Fp2x,
+// the lane pair) and the host twins (Fp2p: tests/hostcheck hc_sgb_group for
+// the classic schedule, tests/sgbpair sp_group for the paired one) run the
+// same code.
 //
 // FAST = true adds with jac_add_x (bls_pair.h): no doubling branch, `exc` set
 // when an addition met two equal operands, the result then unusable.  Equal
@@ -44,6 +45,56 @@ TBG_HD Jac<F> sgb_running_sums_g(L&& bucket, uint32_t n_v, bool& exc) {
     q = sgb_add_g<F, FAST>(q, run, exc);
   }
   return q;
+}
+
+// ---- paired schedule (k_sgb.hip): buckets over two combinations' digits ----
+// Member i of a group goes, for the pair p of combinations (2p, 2p + 1), into
+// the bucket (a, b) = +-(c_i,2p, c_i,2p+1), the sign -- the member's point is
+// negated with it -- chosen so that a > 0, or a = 0 and b > 0; (0, 0) is in
+// no sum.  The 84 buckets of a pair: a = 0 with b = 1..6, then the rows
+// a = 1..6 with b = -6..6.
+constexpr uint32_t SGBP_V = 6;                           // digits -6..6
+constexpr uint32_t SGBP_ROW = 2 * SGBP_V + 1;            // buckets of a row a >= 1
+constexpr uint32_t SGBP_B = SGBP_V + SGBP_V * SGBP_ROW;  // buckets per pair
+constexpr uint32_t SGBP_SUMS = 2 * SGBP_V;               // R_1..R_6, D_1..D_6
+constexpr uint32_t SGBP_NONE = 0xFFu;                    // sgb_pair_code of (0, 0)
+// (a, b) normalised as above -> the bucket's index in its pair
+TBG_HD uint32_t sgb_pair_index(uint32_t a, int32_t b) {
+  return a ? SGBP_V + (a - 1) * SGBP_ROW + (uint32_t)(b + (int32_t)SGBP_V) : (uint32_t)b - 1;
+}
+// digits (c0, c1) of a member -> bucket index | negated << 7, or SGBP_NONE
+TBG_HD uint32_t sgb_pair_code(int32_t c0, int32_t c1) {
+  if (!c0 && !c1) return SGBP_NONE;
+  const bool neg = c0 < 0 || (!c0 && c1 < 0);
+  return sgb_pair_index((uint32_t)(neg ? -c0 : c0), neg ? -c1 : c1) | (neg ? 0x80u : 0u);
+}
+// The pair's two combinations from its bucket sums B(a, b), as the classic
+// schedule's folded buckets (k_sgb_fold; sgb_running_sums_g then gives
+//   Q_2p = sum_a a R_a,  Q_2p+1 = sum_v v D_v):
+//   sum j = a - 1 (a = 1..6):      R_a = sum_b B(a, b)
+//   sum j = 6 + v - 1 (v = 1..6):  D_v = sum_(a = 0..6) B(a, v) - sum_(a = 1..6) B(a, -v)
+// 13 terms each; bucket(idx) loads the pair's bucket idx.  Empty buckets
+// (infinity) are common and handled by the additions; two equal operands
+// set `exc` under FAST, as in the sums above.
+template <class F, bool FAST, class L>
+TBG_HD Jac<F> sgb_pair_sum_g(L&& bucket, uint32_t j, bool& exc) {
+  Jac<F> acc = jac_inf<F>();
+#pragma unroll 1
+  for (uint32_t t = 0; t < SGBP_ROW; ++t) {
+    uint32_t idx;
+    bool neg = false;
+    if (j < SGBP_V) {
+      idx = sgb_pair_index(j + 1, (int32_t)t - (int32_t)SGBP_V);
+    } else {
+      const int32_t v = (int32_t)(j - SGBP_V) + 1;
+      neg = t > SGBP_V;
+      idx = t == 0 ? sgb_pair_index(0, v) : sgb_pair_index(neg ? t - SGBP_V : t, neg ? -v : v);
+    }
+    Jac<F> x = bucket(idx);
+    if (neg) x = jac_neg(x);
+    acc = sgb_add_g<F, FAST>(acc, x, exc);
+  }
+  return acc;
 }
 
 }  // namespace tbg

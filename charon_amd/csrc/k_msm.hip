@@ -324,7 +324,7 @@ __global__ void __launch_bounds__(2 * L0F_PAIRS) k_l0f_reduce(DevBatch B, uint32
 #pragma unroll 1
   for (uint32_t a = a0; a < a1; ++a) {  // (pair-uniform)
     if (qcol) {
-      acc = jac_add_in<Fp2x, true>(acc, px_load(B.sgb_part[((size_t)SGB_BUCKETS * a + (size_t)SGB_V * col) * B.sgb_split]));
+      acc = jac_add_in<Fp2x, true>(acc, px_load(B.sgb_part[sgb_q_slot(B, a, col)]));
     } else {
       acc = jac_add_in<Fp2x, true>(acc, px_load(B.sgb_t[a]));
     }

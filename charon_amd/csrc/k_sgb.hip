@@ -21,9 +21,32 @@
 //
 //   k_sgb_sort    one workgroup per group: digits, bucket counts and entries in LDS
 //   k_sgb_bucket  one lane PAIR per (group, bucket, slice): the slice's sum
+//   k_sgb_fold    one lane PAIR per (group, bucket): the sum of its slices
 //   k_sgb_combine one lane PAIR per (group, combination): Q_k from its buckets
 //   k_sgb_test    one lane PAIR per (group, combination): psi(Q_k) == [x] Q_k
 // then k_subgroup_sigs tests the members of failed groups one by one.
+//
+// Paired schedule (groups of SGB_PAIR_M = 256 members and more; tbls_launch.h,
+// bls_sgb.h).  The one-dimensional buckets (k, |c_ik|) are Pippenger with the
+// smallest window.  The 18 sums are separate outputs, but a member may be
+// sorted by two of its digits at once: for the pairs (2p, 2p + 1), p = 0..8,
+// member i goes into bucket (a, b) = +-(c_i,2p, c_i,2p+1) with the sign (and
+// the point) chosen so that a > 0, or a = 0 and b > 0 -- 84 buckets per pair,
+// 756 per group, one mixed addition per member per PAIR: 9 x 168/169 = 8.9
+// instead of 16.6.  Both sums come out of the 84 bucket sums B(a, b):
+//   R_a = sum_b B(a, b),                                Q_2p   = sum_a a R_a
+//   D_v = sum_(a>=0) B(a, v) - sum_(a>=1) B(a, -v),     Q_2p+1 = sum_v v D_v
+// (k_sgb_fold: 12 sums of 13 terms per pair, written where the classic
+// schedule leaves its folded buckets, so k_sgb_combine and k_sgb_test run
+// unchanged).  Every Q_k is the same group element as in the classic
+// schedule, so the soundness argument above and the fused level 0 carry over
+// word for word.  A bucket holds ~6 members of 1,024 with a wide spread
+// (0..15), and a wave runs as long as its longest bucket: k_sgb_sort also
+// ranks the group's buckets by entry count (a counting sort in LDS) and
+// k_sgb_bucket hands the 32 lane pairs of a wave consecutive ranks -- 9.4
+// wave iterations per member instead of 14.9 in index order (19.3 classic;
+// DESIGN section 4 has the table and the threshold).
+//
 // With the fused level 0 (bls_rlc.h, top) the same sums serve level 0's
 // S = sum r_i s_i: k_sgb_sort also stores the digits of r_i, k_sgb_bucket also
 // adds the group's unweighted sum T, and a failed group voids level 0.
@@ -42,10 +65,114 @@ namespace tbg {
 #endif
 constexpr uint32_t kSgbSortBlock = TBG_SGB_SORT_BLOCK;  // threads per group's sort
 
+static_assert(SGBP_B == SGB_PB && SGBP_V == SGB_V && SGBP_SUMS * SGB_PAIRS == SGB_BUCKETS, "bls_sgb.h's pair layout");
+static_assert((kSgbSortBlock & (kSgbSortBlock - 1)) == 0, "sgb_block_scan: a power of two");
+constexpr uint32_t SGB_RANK_KEYS = 256;  // bucket sizes 0..254 apart, larger ones together
+
+// a[0..N) -> its exclusive prefix sums, a[N] = the total; every thread of the
+// workgroup calls it (each scans ceil(N / block) consecutive values, the
+// block's partial sums by doubling steps in tmp[block])
+template <uint32_t N>
+__device__ __forceinline__ void sgb_block_scan(uint32_t* a, uint32_t* tmp) {
+  constexpr uint32_t PER = (N + kSgbSortBlock - 1) / kSgbSortBlock;
+  const uint32_t t = threadIdx.x, b0 = t * PER;
+  uint32_t sum = 0;
+  for (uint32_t j = 0; j < PER; ++j)
+    if (b0 + j < N) sum += a[b0 + j];
+  tmp[t] = sum;
+  __syncthreads();
+  for (uint32_t d = 1; d < kSgbSortBlock; d <<= 1) {
+    const uint32_t x = t >= d ? tmp[t - d] : 0u;
+    __syncthreads();
+    tmp[t] += x;
+    __syncthreads();
+  }
+  uint32_t run = tmp[t] - sum;
+  for (uint32_t j = 0; j < PER; ++j)
+    if (b0 + j < N) {
+      const uint32_t x = a[b0 + j];
+      a[b0 + j] = run;
+      run += x;
+    }
+  if (t == kSgbSortBlock - 1) a[N] = tmp[t];
+  __syncthreads();
+}
+
+// k_sgb_sort for a group on the paired schedule: SGB_PAIRS entries per
+// member, SGB_PBUCKETS buckets, and the buckets ranked by decreasing entry
+// count for k_sgb_bucket; `lds` is the workgroup's digit array, reused for
+// one byte per (member, pair) and the sort's own arrays
+__device__ __forceinline__ void sgb_sort_paired(const DevBatch& B, uint8_t* lds) {
+  // (carved from the classic schedule's digit array: the kernel's LDS, and with it its occupancy, stay)
+  uint8_t* code = lds;                                        // [SGB_M][SGB_PAIRS]
+  uint32_t* cnt = (uint32_t*)(lds + SGB_M * SGB_PAIRS);       // [SGB_PBUCKETS + 1]
+  uint32_t* hist = cnt + SGB_PBUCKETS + 1;                    // [SGB_RANK_KEYS + 1]
+  uint32_t* tmp = hist + SGB_RANK_KEYS + 1;                   // [kSgbSortBlock]
+  uint8_t* key = (uint8_t*)(tmp + kSgbSortBlock);             // [SGB_PBUCKETS]
+  static_assert((SGB_M * SGB_PAIRS) % 4 == 0 &&
+                    SGB_M * SGB_PAIRS + 4 * (SGB_PBUCKETS + 1 + SGB_RANK_KEYS + 1 + kSgbSortBlock) + SGB_PBUCKETS <=
+                        SGB_M * SGB_K,
+                "the paired sort's arrays fit the digit array");
+  const uint32_t g = blockIdx.x, t = threadIdx.x, m = B.sgb_m;
+  const uint32_t i0 = g * m;
+  const uint32_t n = min(m, B.n_partials - i0);
+  for (uint32_t b = t; b < SGB_PBUCKETS; b += kSgbSortBlock) cnt[b] = 0;
+  for (uint32_t b = t; b < SGB_RANK_KEYS; b += kSgbSortBlock) hist[b] = 0;
+  if (t == 0) B.sgb_bad[g] = 0;
+  const bool fused = l0_fused(B);
+  __syncthreads();
+  for (uint32_t li = t; li < n; li += kSgbSortBlock) {
+    const bool ok = B.partial_status[i0 + li] == TBG_PS_NOT_VERIFIED;
+    int32_t c[SGB_K];
+    sgb_digits(B.sgb_seed, i0 + li, c);
+    if (fused) {  // (as in k_sgb_sort below)
+      uint32_t u[4];
+      l0f_digits(c, u);
+      *(uint4*)(B.l0f_u + 4ull * (i0 + li)) = make_uint4(u[0], u[1], u[2], u[3]);
+    }
+#pragma unroll
+    for (uint32_t p = 0; p < SGB_PAIRS; ++p) {
+      const uint32_t cd = ok ? sgb_pair_code(c[2 * p], c[2 * p + 1]) : SGBP_NONE;
+      code[li * SGB_PAIRS + p] = (uint8_t)cd;
+      if (cd != SGBP_NONE) atomicAdd(&cnt[p * SGB_PB + (cd & 0x7Fu)], 1u);
+    }
+  }
+  __syncthreads();
+  for (uint32_t b = t; b < SGB_PBUCKETS; b += kSgbSortBlock) {  // larger buckets first
+    const uint32_t k = SGB_RANK_KEYS - 1 - min(cnt[b], SGB_RANK_KEYS - 1);
+    key[b] = (uint8_t)k;
+    atomicAdd(&hist[k], 1u);
+  }
+  __syncthreads();
+  sgb_block_scan<SGB_PBUCKETS>(cnt, tmp);
+  sgb_block_scan<SGB_RANK_KEYS>(hist, tmp);
+  uint32_t* goff = B.sgb_off + (size_t)(SGB_PBUCKETS + 1) * g;
+  uint32_t* rank = B.sgb_rank + (size_t)SGB_PBUCKETS * g;
+  for (uint32_t b = t; b <= SGB_PBUCKETS; b += kSgbSortBlock) {
+    goff[b] = cnt[b];
+    if (b < SGB_PBUCKETS) rank[atomicAdd(&hist[key[b]], 1u)] = b;  // (every rank 0..755 once)
+  }
+  __syncthreads();  // cnt: now the scatter cursors
+  uint32_t* ent = B.sgb_ent + (size_t)sgb_ent_stride(m) * g;
+  for (uint32_t li = t; li < n; li += kSgbSortBlock) {
+#pragma unroll 1
+    for (uint32_t p = 0; p < SGB_PAIRS; ++p) {
+      const uint32_t cd = code[li * SGB_PAIRS + p];
+      if (cd == SGBP_NONE) continue;
+      const uint32_t pos = atomicAdd(&cnt[p * SGB_PB + (cd & 0x7Fu)], 1u);
+      ent[pos] = (li << 1) | (cd >> 7);
+    }
+  }
+}
+
 __global__ void __launch_bounds__(kSgbSortBlock) k_sgb_sort(DevBatch B) {
   __shared__ uint32_t cnt[SGB_BUCKETS];
   __shared__ uint32_t off[SGB_BUCKETS + 1];
-  __shared__ int8_t dig[SGB_M * SGB_K];  // (the largest group)
+  __shared__ __attribute__((aligned(16))) int8_t dig[SGB_M * SGB_K];  // (the largest group)
+  if (sgb_paired(B.sgb_m)) {  // (grid-uniform)
+    sgb_sort_paired(B, (uint8_t*)dig);
+    return;
+  }
   const uint32_t g = blockIdx.x, t = threadIdx.x, m = B.sgb_m;
   const uint32_t i0 = g * m;
   const uint32_t n = min(m, B.n_partials - i0);
@@ -97,15 +224,25 @@ __global__ void __launch_bounds__(kSgbSortBlock) k_sgb_sort(DevBatch B) {
   }
 }
 
-// one lane pair per (group, bucket, slice); with the fused level 0 the pairs
-// after them, one per (group, SGB_T_PER consecutive members), add the group's
+// one lane pair per (group, bucket, slice) -- on the paired schedule per
+// (group, rank): the SGB_PRANK = 768 pairs of a group take its 756 buckets in
+// the order of k_sgb_sort's ranking, so the 32 pairs of a wave hold buckets
+// of near-equal length (the last 12 are idle); with the fused level 0 further
+// pairs, one per (group, SGB_T_PER consecutive members), add the group's
 // unweighted sum T: one more bucket with coefficient +1 whose members are the
 // candidates at sort time (nothing changes a status between the two kernels)
 __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_bucket(DevBatch B, uint32_t n_sg, uint32_t n_t) {
-  const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;  // both lanes of a pair take the same branches
+  uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;  // both lanes of a pair take the same branches
   const uint32_t S = B.sgb_split, m = B.sgb_m;
-  if (w >= n_sg * SGB_BUCKETS * S) {
-    const uint32_t wt = w - n_sg * SGB_BUCKETS * S;
+  const bool paired = sgb_paired(m);
+  const uint32_t per_g = paired ? SGB_PRANK : SGB_BUCKETS * S;
+  // T's pairs: after the buckets' on the classic schedule; FIRST on the paired
+  // one, whose bucket chains (~12 additions a wave, the last waves of a group
+  // next to none) are shorter than T's 32 -- started last, T's waves were the
+  // grid's tail, a fifth of the kernel's time
+  const bool is_t = paired ? w < n_sg * n_t : w >= n_sg * per_g;
+  if (is_t) {
+    const uint32_t wt = paired ? w : w - n_sg * per_g;
     if (wt >= n_sg * n_t) return;
     const uint32_t i0 = (wt / n_t) * m + (wt % n_t) * SGB_T_PER;
     const uint32_t i1 = min(min(i0 + SGB_T_PER, (wt / n_t + 1) * m), B.n_partials);
@@ -120,11 +257,28 @@ __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_bucket(DevBatch B, uint32_t n
     px_store(B.sgb_t[wt], acc);
     return;
   }
-  const uint32_t g = w / (SGB_BUCKETS * S), b = (w / S) % SGB_BUCKETS, sl = w % S;
-  const uint32_t* goff = B.sgb_off + (size_t)(SGB_BUCKETS + 1) * g;
-  const uint32_t o0 = goff[b], n = goff[b + 1] - o0;
-  const uint32_t e0 = o0 + (n * sl) / S, e1 = o0 + (n * (sl + 1)) / S;
-  const uint32_t* ent = B.sgb_ent + (size_t)m * SGB_K * g;
+  if (paired) w -= n_sg * n_t;
+  if (w >= n_sg * per_g) return;  // (the grid's last wave)
+  const uint32_t g = w / per_g;
+  uint32_t e0, e1;
+  size_t out;
+  if (paired) {
+    const uint32_t r = w % SGB_PRANK;
+    if (r >= SGB_PBUCKETS) return;
+    const uint32_t b = B.sgb_rank[(size_t)SGB_PBUCKETS * g + r];
+    const uint32_t* goff = B.sgb_off + (size_t)(SGB_PBUCKETS + 1) * g;
+    e0 = goff[b];
+    e1 = goff[b + 1];
+    out = (size_t)sgb_part_stride(m) * g + b;
+  } else {
+    const uint32_t b = (w / S) % SGB_BUCKETS, sl = w % S;
+    const uint32_t* goff = B.sgb_off + (size_t)(SGB_BUCKETS + 1) * g;
+    const uint32_t o0 = goff[b], n = goff[b + 1] - o0;
+    e0 = o0 + (n * sl) / S;
+    e1 = o0 + (n * (sl + 1)) / S;
+    out = w;
+  }
+  const uint32_t* ent = B.sgb_ent + (size_t)sgb_ent_stride(m) * g;
   const G2A* sig = B.sig_aff + (size_t)m * g;
   Jac<Fp2x> acc = jac_inf<Fp2x>();
 #pragma unroll 1
@@ -135,7 +289,7 @@ __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_bucket(DevBatch B, uint32_t n
     if (v & 1u) p.y = f_reduce(f_neg(p.y));
     acc = jac_add_aff_in(acc, p);
   }
-  px_store(B.sgb_part[w], acc);
+  px_store(B.sgb_part[out], acc);
 }
 
 // A failed group (k_sgb_test alone decides): its members are tested alone, and
@@ -161,9 +315,29 @@ __device__ __noinline__ Jac<Fp2x> sgb_fold_complete(const G2J* part, uint32_t S)
   return sgb_fold_g<Fp2x, false>([&](uint32_t sl) { return px_load(part[sl]); }, S, unused);
 }
 
+// Paired schedule: one lane pair per (group, pair of combinations, one of its
+// 12 sums R_a, D_v), each 13 bucket sums of which many are empty (bls_sgb.h
+// sgb_pair_sum_g), stored after the group's bucket sums in the layout of the
+// classic schedule's folded buckets.  Equal operands (replayed signatures)
+// are redone in the same way.
+__device__ __noinline__ Jac<Fp2x> sgb_pair_sum_complete(const G2J* bk, uint32_t j) {
+  bool unused = false;
+  return sgb_pair_sum_g<Fp2x, false>([&](uint32_t idx) { return px_load(bk[idx]); }, j, unused);
+}
+
 __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_fold(DevBatch B, uint32_t n_sg) {
   const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;  // both lanes of a pair take the same branches
   if (w >= n_sg * SGB_BUCKETS) return;
+  if (sgb_paired(B.sgb_m)) {
+    const uint32_t g = w / SGB_BUCKETS, p = (w % SGB_BUCKETS) / SGBP_SUMS, j = w % SGBP_SUMS;
+    G2J* grp = B.sgb_part + (size_t)sgb_part_stride(B.sgb_m) * g;
+    const G2J* bk = grp + (size_t)SGB_PB * p;
+    bool exc = false;
+    Jac<Fp2x> acc = sgb_pair_sum_g<Fp2x, true>([&](uint32_t idx) { return px_load(bk[idx]); }, j, exc);
+    if (!pair_all(!exc)) acc = sgb_pair_sum_complete(bk, j);  // (pair-uniform)
+    px_store(grp[SGB_PBUCKETS + w % SGB_BUCKETS], acc);
+    return;
+  }
   const uint32_t S = B.sgb_split;
   G2J* part = B.sgb_part + (size_t)w * S;
   bool exc = false;
@@ -183,8 +357,8 @@ __device__ __noinline__ Jac<Fp2x> sgb_combine_complete(const G2J* part, uint32_t
 __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_combine(DevBatch B, uint32_t n_sg) {
   const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;  // both lanes of a pair take the same branches
   if (w >= n_sg * SGB_K) return;
-  const uint32_t g = w / SGB_K, k = w % SGB_K, S = B.sgb_split;
-  G2J* part = B.sgb_part + ((size_t)SGB_BUCKETS * g + (size_t)SGB_V * k) * S;
+  const uint32_t g = w / SGB_K, k = w % SGB_K, S = sgb_paired(B.sgb_m) ? 1u : B.sgb_split;
+  G2J* part = B.sgb_part + sgb_q_slot(B, g, k);
   bool exc = false;
   Jac<Fp2x> q = sgb_running_sums_g<Fp2x, true>([&](uint32_t v) { return px_load(part[(size_t)v * S]); }, SGB_V, exc);
   if (!pair_all(!exc)) q = sgb_combine_complete(part, S);  // (pair-uniform)
@@ -198,7 +372,7 @@ __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_test(DevBatch B, uint32_t n_s
   const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;
   if (w >= n_sg * SGB_K) return;
   const uint32_t g = w / SGB_K, k = w % SGB_K;
-  const G2J& slot = B.sgb_part[((size_t)SGB_BUCKETS * g + (size_t)SGB_V * k) * B.sgb_split];
+  const G2J& slot = B.sgb_part[sgb_q_slot(B, g, k)];
   bool ok = true;
   if (!jac_is_inf(px_load(slot))) {
     // [|x|] Q with Q re-read from its slot where it is added (held across the
@@ -232,8 +406,10 @@ void launch_subgroup_batch(const DevBatch& B, hipStream_t st) {
   if (!n_sg) return;
   TBG_KLAUNCH(k_sgb_sort, dim3(n_sg), dim3(kSgbSortBlock), st, B);
   const uint32_t n_t = l0_fused(B) ? sgb_t_slices(B.sgb_m) : 0u;  // the slices of T per group
-  TBG_KLAUNCH(k_sgb_bucket, grid_for(2 * n_sg * (SGB_BUCKETS * B.sgb_split + n_t)), dim3(kBlock), st, B, n_sg, n_t);
-  if (B.sgb_split > 1) TBG_KLAUNCH(k_sgb_fold, grid_for(2 * n_sg * SGB_BUCKETS), dim3(kBlock), st, B, n_sg);
+  const bool paired = sgb_paired(B.sgb_m);
+  const uint32_t per_g = paired ? SGB_PRANK : SGB_BUCKETS * B.sgb_split;  // k_sgb_bucket's lane pairs per group
+  TBG_KLAUNCH(k_sgb_bucket, grid_for(2 * n_sg * (per_g + n_t)), dim3(kBlock), st, B, n_sg, n_t);
+  if (paired || B.sgb_split > 1) TBG_KLAUNCH(k_sgb_fold, grid_for(2 * n_sg * SGB_BUCKETS), dim3(kBlock), st, B, n_sg);
   TBG_KLAUNCH(k_sgb_combine, grid_for(2 * n_sg * SGB_K), dim3(kBlock), st, B, n_sg);
   TBG_KLAUNCH(k_sgb_test, grid_for(2 * n_sg * SGB_K), dim3(kBlock), st, B, n_sg);
 }

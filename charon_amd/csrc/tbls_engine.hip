@@ -672,7 +672,10 @@ static bool l0_shape_fits(uint32_t nd0, uint32_t G0, uint32_t C0, uint32_t nd, u
 // cheapest power of two in [SGB_M_MIN, SGB_M]; the test runs while that
 // costs under 0.95 of testing every signature alone -- up to rho ~ 2.5e-3
 // (TBG_SGB_AUTO_MAX).  Clean traffic keeps m = 1,024; config 5's 1.25e-3
-// takes m = 128 (at 1,024, 72 % of its groups would fail).
+// takes m = 128 (at 1,024, 72 % of its groups would fail).  The 0.55 is the
+// classic schedule's; the paired schedule of groups >= SGB_PAIR_M
+// (tbls_launch.h) is cheaper, which only widens the test's margin, and the
+// sizes this plan picks are left as they were.
 static bool sgb_plan(double rho, uint32_t& m) {
   double best = 1e9;
   m = SGB_M;
@@ -830,9 +833,10 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
                    (sgb_plan(c->nonsub_ema, sgb_m) || c->sgb_mode == TBG_SGB_ON);
   const uint32_t sgb_split = sgb_split_for(sgb_m);
   const size_t n_sg = sgb ? sgb_groups(np, sgb_m) : 0;
-  size_t w_sgoff = sec(4ull * (SGB_BUCKETS + 1) * n_sg);
-  size_t w_sgent = sec(4ull * sgb_m * SGB_K * n_sg);
-  size_t w_sgpart = sec(sizeof(G2J) * SGB_BUCKETS * sgb_split * n_sg);
+  size_t w_sgoff = sec(4ull * sgb_off_stride(sgb_m) * n_sg);
+  size_t w_sgent = sec(4ull * sgb_ent_stride(sgb_m) * n_sg);
+  size_t w_sgpart = sec(sizeof(G2J) * sgb_part_stride(sgb_m) * n_sg);
+  size_t w_sgrank = sec(sgb_paired(sgb_m) ? 4ull * SGB_PBUCKETS * n_sg : 0);
   size_t w_sgbad = sec(4ull * n_sg);
   // Level 0's signature side: with the batched test on, S comes from the
   // test's sums (l0_fused, tbls_launch.h; a replayed prefix of the launch
@@ -1108,6 +1112,7 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   B.sgb_off = (uint32_t*)(dw + w_sgoff);
   B.sgb_ent = (uint32_t*)(dw + w_sgent);
   B.sgb_part = (G2J*)(dw + w_sgpart);
+  B.sgb_rank = (uint32_t*)(dw + w_sgrank);
   B.sgb_bad = (uint32_t*)(dw + w_sgbad);
   B.sgb_t = (G2J*)(dw + w_sgt);
   B.l0f_sum = (G2J*)(dw + w_l0fsum);
@@ -1526,6 +1531,18 @@ int tbg_fetch_subgroup(tbg_ctx* c, tbg_ticket t, uint32_t* out3) {
   HIP_TRY(hipStreamSynchronize(s->st));
   out3[0] = n_sg;
   for (uint32_t g = 0; g < n_sg; ++g) out3[1] += bad[g] ? 1u : 0u;
+  return TBG_OK;
+}
+
+int tbg_fetch_subgroup_schedule(tbg_ctx* c, tbg_ticket t, uint32_t* out1) {
+  if (!c || !out1) return TBG_E_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(c->mu);
+  Slot* s = find_ticket(c, t, false, nullptr);
+  if (!s) return TBG_E_TICKET;
+  // (the launch's own fields: the kernels took their schedule from the same ones)
+  *out1 = !s->last.sgb                 ? (uint32_t)TBG_SGB_SCHED_NONE
+          : sgb_paired(s->last.sgb_m) ? (uint32_t)TBG_SGB_SCHED_PAIRED
+                                      : (uint32_t)TBG_SGB_SCHED_CLASSIC;
   return TBG_OK;
 }
 

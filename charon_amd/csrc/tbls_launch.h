@@ -189,9 +189,10 @@ struct DevBatch {
   uint32_t sgb_seed[8];   // secret per-batch key of the combinations' digits: always fresh OS
                           // entropy, even under a fixed rlc_seed (a predictable key would let a
                           // submitter craft torsion components that cancel across combinations)
-  uint32_t* sgb_off;      // [n_sg][SGB_BUCKETS + 1] bucket offsets into the group's entries
-  uint32_t* sgb_ent;      // [n_sg][sgb_m * SGB_K] entries: member << 1 | negative
-  G2J* sgb_part;          // [n_sg][SGB_BUCKETS][sgb_split] bucket slice sums
+  uint32_t* sgb_off;      // [n_sg][sgb_off_stride] bucket offsets into the group's entries
+  uint32_t* sgb_ent;      // [n_sg][sgb_ent_stride] entries: member << 1 | negative
+  G2J* sgb_part;          // [n_sg][sgb_part_stride] bucket (slice) sums; Q_k at sgb_q_slot
+  uint32_t* sgb_rank;     // [n_sg][SGB_PBUCKETS] paired schedule: the group's buckets by decreasing entry count
   uint32_t* sgb_bad;      // [n_sg] 1: some combination is outside G2 (members tested alone)
   // fused level 0 (l0_fused below): S from the subgroup test's sums
   G2J* sgb_t;             // [n_sg][sgb_t_slices(sgb_m)] slice sums of the group's unweighted candidates
@@ -262,6 +263,32 @@ TBG_HD uint32_t sgb_groups(uint32_t n_partials, uint32_t m) { return (n_partials
 TBG_HD uint32_t sgb_split_for(uint32_t m) {
   const uint32_t s = SGB_SPLIT * m / SGB_M;
   return s ? s : 1u;
+}
+// Paired schedule (k_sgb.hip) for groups of at least SGB_PAIR_M: a member is
+// sorted by two of its digits at once, (c_2p, c_2p+1) for the SGB_PAIRS pairs
+// of combinations, into one of SGB_PB two-dimensional buckets per pair -- one
+// addition per pair instead of one per combination; no slices.  Smaller
+// groups keep the classic one-dimensional buckets: the paired reductions
+// (~1,500 additions per group whatever its size) and its many short buckets
+// cost more than the halved bucket additions save.
+constexpr uint32_t SGB_PAIR_M = 256;
+constexpr uint32_t SGB_PAIRS = SGB_K / 2;
+constexpr uint32_t SGB_PB = SGB_V + SGB_V * (2 * SGB_V + 1);  // 84: a = 0 has b = 1..6, a = 1..6 has b = -6..6
+constexpr uint32_t SGB_PBUCKETS = SGB_PAIRS * SGB_PB;         // 756 per group
+constexpr uint32_t SGB_PRANK = (SGB_PBUCKETS + 31) / 32 * 32;  // k_sgb_bucket's lane pairs per group: whole waves
+TBG_HD bool sgb_paired(uint32_t m) { return m >= SGB_PAIR_M; }
+// per-group strides of sgb_off, sgb_ent and sgb_part in either schedule
+// (paired: the SGB_PBUCKETS bucket sums, then the SGB_BUCKETS sums of
+// k_sgb_fold laid out as the classic schedule's folded buckets)
+TBG_HD uint32_t sgb_off_stride(uint32_t m) { return (sgb_paired(m) ? SGB_PBUCKETS : SGB_BUCKETS) + 1; }
+TBG_HD uint32_t sgb_ent_stride(uint32_t m) { return m * (sgb_paired(m) ? SGB_PAIRS : SGB_K); }
+TBG_HD uint32_t sgb_part_stride(uint32_t m) {
+  return sgb_paired(m) ? SGB_PBUCKETS + SGB_BUCKETS : SGB_BUCKETS * sgb_split_for(m);
+}
+// Q_k of group g (k_sgb_combine's output; k_sgb_test and the fused level 0 read it)
+TBG_HD size_t sgb_q_slot(const DevBatch& B, uint32_t g, uint32_t k) {
+  return (size_t)sgb_part_stride(B.sgb_m) * g +
+         (sgb_paired(B.sgb_m) ? SGB_PBUCKETS + SGB_V * k : SGB_V * k * B.sgb_split);
 }
 // Fused level 0 (bls_rlc.h, k_msm.hip): while the batched subgroup test runs,
 // r_i is a fixed linear form of the partial's 18 subgroup digits, so S is a

@@ -30,6 +30,7 @@ VERIFY_RLC, VERIFY_EACH = 0, 1
 RLC_L0_AUTO, RLC_L0_ON, RLC_L0_OFF = 0, 1, 2   # tbg_config.rlc_batch
 GIDENT_OFF, GIDENT_L3, GIDENT_CHUNKS = 0, 1, 2  # tbg_config.gident
 SGB_AUTO, SGB_ON, SGB_OFF = 0, 1, 2           # tbg_config.subgroup_batch
+SGB_SCHEDULES = ("none", "classic", "paired")  # TBG_SGB_SCHED_* (tbg_fetch_subgroup_schedule)
 EXPRESS_OFF = 0xFFFFFFFF                        # tbg_config.express_partials: no express slot
 L0_NOT_RUN, L0_PASSED, L0_FAILED = 0, 1, 2     # tbg_fetch_level0
 HOST_STAT_KEYS = ["submits", "partials_submitted", "pack_ns", "enqueue_ns", "collects", "partials_collected",
@@ -309,13 +310,21 @@ class Engine:
         self._check(self._lib.tbg_fetch_shape(self._h, ticket, _ptr(out)), "tbg_fetch_shape")
         return dict(zip(["group", "chunk", "level0", "chunks"], out.tolist()))
 
-    def subgroup(self, ticket) -> dict:
+    def subgroup(self, ticket, schedule: bool = False) -> dict:
         """Batched subgroup test of the batch's last run (tbg_fetch_subgroup):
         groups of consecutive partials tested by random combinations (0:
-        every signature tested alone), how many failed, partials per group."""
+        every signature tested alone), how many failed, partials per group.
+        With `schedule`, also the key "schedule": which schedule its kernels
+        took (tbg_fetch_subgroup_schedule: "none", "classic" or "paired")."""
         out = np.zeros(3, dtype=np.uint32)
         self._check(self._lib.tbg_fetch_subgroup(self._h, ticket, _ptr(out)), "tbg_fetch_subgroup")
-        return dict(zip(["groups", "failed", "group_size"], out.tolist()))
+        res = dict(zip(["groups", "failed", "group_size"], out.tolist()))
+        if schedule:
+            sched = np.zeros(1, dtype=np.uint32)
+            self._check(self._lib.tbg_fetch_subgroup_schedule(self._h, ticket, _ptr(sched)),
+                        "tbg_fetch_subgroup_schedule")
+            res["schedule"] = SGB_SCHEDULES[int(sched[0])]
+        return res
 
     def host_stats(self, reset=False) -> dict:
         """Host-side work of this context's submit / collect calls (tbg_host_stats)."""

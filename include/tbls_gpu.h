@@ -317,6 +317,15 @@ int tbg_fetch_fallback(tbg_ctx* ctx, tbg_ticket ticket, uint32_t* out8);
  * combinations (0: every signature was tested alone), groups that failed
  * (their members were then tested one by one), partials per group]. */
 int tbg_fetch_subgroup(tbg_ctx* ctx, tbg_ticket ticket, uint32_t* out3);
+/* Which schedule the batched subgroup test of the batch's last run took
+ * (read-only, no device work): *out1 = TBG_SGB_SCHED_NONE (every signature
+ * was tested alone), TBG_SGB_SCHED_CLASSIC (one bucket per combination and
+ * digit size: groups below 256 partials) or TBG_SGB_SCHED_PAIRED (buckets over
+ * two combinations' digits at once: groups of 256 and more). */
+#define TBG_SGB_SCHED_NONE 0
+#define TBG_SGB_SCHED_CLASSIC 1
+#define TBG_SGB_SCHED_PAIRED 2
+int tbg_fetch_subgroup_schedule(tbg_ctx* ctx, tbg_ticket ticket, uint32_t* out1);
 /* Verification shape of a collected batch's last submit: out4 = [duties per
  * group G, duties per Miller chunk C, level 0 on (1) or off, Miller P-chunk
  * hexads G x C cut the batch into].  A level-0 launch with neither G nor C

@@ -139,16 +139,19 @@ def main():
     duty_sum4 -= saved
     rlc_partial -= saved  # (k_rlc_partial2: the n2 inversion batched; its G1 product now from the key's table)
     hash_ -= 2 * saved
-    # batched subgroup test (k_sgb.hip, SGB_M = 1024, 18 combinations with
-    # digits uniform mod 13: 12/13 of them non-zero): per partial 18 * 12 / 13
-    # mixed additions into buckets; per group and combination the running
-    # sums over 6 buckets x 4 slices (30 additions) and one psi(Q) == [x]Q
-    # test on a Jacobian Q (the affine test with its 5 mixed additions full)
+    # batched subgroup test (k_sgb.hip, SGB_M = 1024: the paired schedule; 18
+    # combinations with digits uniform mod 13 taken two at a time, 168/169 of
+    # the digit pairs non-zero): per partial 9 * 168 / 169 mixed additions
+    # into buckets; per group and pair of combinations the 12 sums of 13
+    # bucket sums (12 additions each, the empty buckets' trivial ones counted
+    # in full), per combination the running sums over 6 of them and one
+    # psi(Q) == [x]Q test on a Jacobian Q (the affine test with its 5 mixed
+    # additions full)
     madd, _ = measure(lib.hc_k_msm_entry, 0)  # k = 0: psi^0, one mixed addition
     sgb_m, sgb_k = 1024, 18
-    sgb_bucket = sgb_k * 12 / 13 * madd
-    sgb_fold = sgb_k * 6 * 3 * g2_add / sgb_m  # each bucket's 4 slices into one
-    sgb_combine = sgb_k * 12 * g2_add / sgb_m  # the running sums over the 6 folded buckets
+    sgb_bucket = sgb_k / 2 * 168 / 169 * madd
+    sgb_fold = sgb_k / 2 * 12 * 12 * g2_add / sgb_m  # R_a, D_v of every pair
+    sgb_combine = sgb_k * 12 * g2_add / sgb_m  # the running sums over the 6 folded sums
     sgb_test = sgb_k * (k_subgroup + 5 * (g2_add - madd)) / sgb_m
     sgb_per_partial = sgb_bucket + sgb_fold + sgb_combine + sgb_test
     decode_sgb = k_decode + sgb_per_partial
