@@ -208,6 +208,7 @@ class TbgConfig(ctypes.Structure):
         ("fb_window", ctypes.c_uint32),
         ("subgroup_batch", ctypes.c_uint32),
         ("express_partials", ctypes.c_uint32),
+        ("l0_duty_partials", ctypes.c_uint32),
     ]
 
 

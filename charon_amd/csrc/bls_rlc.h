@@ -246,6 +246,41 @@ TBG_HD Jac<F> rlc_mul_key_l0f(const Aff<F>* tab, const Fp& c, const uint32_t (&u
   return acc;
 }
 
+// Fused level 0's key side of one duty in Straus' joint form,
+//   P_d = sum_i [r_i] pk_i = sum_w 4^w sum_i E_(i,w),
+// E_(i,w) the table entries rlc_mul_key_l0f adds for window w of partial i:
+// the 18 doublings run once per duty instead of once per candidate.
+// cand(k, tab, u) says whether the duty's k-th partial is a candidate and, if
+// so, gives its key's window table and its four digits.  The additions meet
+// points of different keys -- and of one key named twice, so equal operands
+// (equal window digits), opposite operands and an infinite accumulator are
+// all legal input: `add` must be complete (jac_add_aff_in; the host control
+// passes the addition without the doubling branch).  Infinity for a duty
+// without candidates.
+template <class F, class Cand, class Add>
+TBG_HD Jac<F> rlc_duty_keys_l0f(uint32_t n, const Fp& c, Cand&& cand, Add&& add) {
+  Jac<F> acc = jac_inf<F>();
+#pragma unroll 1
+  for (int w = 9; w >= 0; --w) {
+    if (w < 9) acc = jac_dbl_in(jac_dbl_in(acc));  // (infinity stays infinity: Z3 = 2 Y Z)
+#pragma unroll 1
+    for (uint32_t k = 0; k < n; ++k) {
+      const Aff<F>* tab;
+      uint32_t u[4];
+      if (!cand(k, tab, u)) continue;
+      // windows 9 and 8 have no phi entry (u_2, u_3 < 2^16), as in rlc_mul_key_l0f
+#pragma unroll 1
+      for (int h = 0; h < (w < 8 ? 2 : 1); ++h)
+        acc = add(acc, rlc_entry_w2(tab, rlc_win2(h ? u[2] : u[0], w), rlc_win2(h ? u[3] : u[1], w), h != 0, c));
+    }
+  }
+  return acc;
+}
+template <class F, class Cand>
+TBG_HD Jac<F> rlc_duty_keys_l0f(uint32_t n, const Fp& c, Cand&& cand) {
+  return rlc_duty_keys_l0f<F>(n, c, cand, [](const Jac<F>& p, const Aff<F>& q) { return jac_add_aff_in(p, q); });
+}
+
 // [r] pk from the key's resident table (PK_TAB entries, tbls_launch.h)
 #if defined(TBG_PK_W2)
 TBG_HD G1J rlc_mul_key(const G1A* tab, const uint32_t (&u)[4]) {

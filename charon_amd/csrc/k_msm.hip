@@ -72,6 +72,8 @@ __global__ void __launch_bounds__(BINV_BLOCK) k_pubkey_tables(const G1A* pk, con
 // candidate's r_i is drawn (no group lead: at level 0 two r = 1 partials of
 // different groups could cancel) and [r_i] pk_i computed from the key's pair
 // table; the four digits count into their buckets.
+// (Fused launches of at least l0_duty_partials partials run l0duty::k_rlc_g1_l0
+// below instead.)
 __global__ void TBG_LAUNCH k_rlc_g1_l0(DevBatch B, const G1A* tab, const int32_t* pk_status, uint32_t n_pk) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B.n_partials || B.partial_status[i] != TBG_PS_NOT_VERIFIED) return;
@@ -99,6 +101,70 @@ __global__ void TBG_LAUNCH k_rlc_g1_l0(DevBatch B, const G1A* tab, const int32_t
     atomicAdd(&B.msm_off[msm_bucket(u[k], neg)], 1u);
   }
 }
+
+// Level-0 G1 side of a fused launch of at least l0_duty_partials partials
+// (l0_per_duty): a kernel of its own behind the same profile name, so that
+// the per-partial kernel above compiles as it always did.  One lane per
+// DUTY: the key marks of the duty's partials, then P_d in Straus' joint form
+// over its candidates (rlc_duty_keys_l0f: the 18 doublings once per duty, not
+// once per candidate; part_p is not written), its affine conversion batched
+// over the workgroup, and dv_p / dv_state as k_rlc_duty_sum<DSUM_L0_P> writes
+// them -- that kernel is not launched then.  (Two lanes per duty, each with
+// every second partial and one Jacobian addition to join them, measured a
+// smaller headline gain: DESIGN section 6-r11.)
+// A duty has no bound on its partials, so the candidates' ids and digits are
+// read again in every window (one uint4 and two words per candidate, beside
+// its two table entries).
+namespace l0duty {
+static_assert(BINV_BLOCK == kBlock, "k_rlc_g1_l0: the workgroup of the batched inversion");
+__global__ void TBG_LAUNCH k_rlc_g1_l0(DevBatch B, const G1A* tab, const int32_t* pk_status, uint32_t n_pk) {
+  const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = d < B.n_duties;
+  uint32_t i0 = 0, n = 0, cand = 0;
+  if (in) {
+    i0 = B.duty_first[d];
+    n = B.duty_first[d + 1] - i0;
+    for (uint32_t k = 0; k < n; ++k) {
+      const uint32_t i = i0 + k;
+      if (B.partial_status[i] != TBG_PS_NOT_VERIFIED) continue;
+      const uint32_t pid = B.pubkey_ids[i];
+      if (pid >= n_pk || pk_status[pid] != DEC_OK) {
+        B.partial_status[i] = TBG_PS_ERR_PUBKEY;
+        B.counters[CNT_L0_BAD] = 1;  // the fused S holds this partial: level 0 is void
+        continue;
+      }
+      ++cand;
+    }
+  }
+  G1J P = jac_inf<Fp>();
+  if (cand)
+    P = rlc_duty_keys_l0f<Fp>(n, fp_from_const(G1_BETA), [&](uint32_t k, const G1A*& e, uint32_t (&u)[4]) {
+      const uint32_t i = i0 + k;
+      if (B.partial_status[i] != TBG_PS_NOT_VERIFIED) return false;  // (this lane's own marks included)
+      e = tab + (size_t)PK_TAB * B.pubkey_ids[i];
+      const uint4 v = *(const uint4*)(B.l0f_u + 4ull * i);
+      u[0] = v.x;
+      u[1] = v.y;
+      u[2] = v.z;
+      u[3] = v.w;
+      return true;
+    });
+  G1A Pa;
+  const bool aff = block_jac_to_aff<BINV_WAVES>(P, cand > 0, Pa);  // every thread of the workgroup
+  if (!in) return;
+  if (cand == 0) {
+    B.dv_state[d] = RLC_NONE;
+    return;
+  }
+  if (!aff) {
+    B.dv_state[d] = RLC_EACH;  // degenerate combination: check the partials one by one
+    B.counters[CNT_L0_BAD] = 1;
+    return;
+  }
+  B.dv_p[d] = G1A{fp_reduce(fp_neg(Pa.x)), Pa.y};  // (-x, y): the Miller steps' evaluation operands
+  B.dv_state[d] = RLC_COMBINED;
+}
+}  // namespace l0duty
 
 // Exclusive scan of the bucket sizes into offsets (msm_off) and cursors
 // (msm_cur): one workgroup of 1024 lanes, 32 buckets per lane.
@@ -378,6 +444,11 @@ void launch_pubkey_tables(const G1A* pk, const G1A* xpk, const int32_t* status, 
 // (after it the candidates are final: the speculative aggregation may run).
 void launch_l0_keys(const DevBatch& B, const G1A* pk_tab, const int32_t* pk_status, uint32_t n_pk, hipStream_t st) {
   // (msm_off was zeroed by k_decode_sigs, the chain's first kernel)
+  if (l0_per_duty(B)) {  // P_d and dv_state too; the same name in the per-kernel profile
+    using l0duty::k_rlc_g1_l0;
+    TBG_KLAUNCH(k_rlc_g1_l0, grid_for(B.n_duties), dim3(kBlock), st, B, pk_tab, pk_status, n_pk);
+    return;
+  }
   if (B.n_partials) TBG_KLAUNCH(k_rlc_g1_l0, grid_for(B.n_partials), dim3(kBlock), st, B, pk_tab, pk_status, n_pk);
 }
 

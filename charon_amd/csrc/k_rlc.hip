@@ -907,7 +907,8 @@ void launch_rlc_prepare(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff
     // S: from the subgroup test's sums while the batched test runs, else the bucket MSM
     if (l0_fused(B)) launch_l0_fused_s(B, st);
     else launch_l0_msm(B, st);
-    TBG_KLAUNCH(k_rlc_duty_sum<DSUM_L0_P>, duty_grid(B), dim3(BINV_BLOCK), st, B);
+    // (a per-duty key side has written P_d and dv_state itself: k_rlc_g1_l0)
+    if (!l0_per_duty(B)) TBG_KLAUNCH(k_rlc_duty_sum<DSUM_L0_P>, duty_grid(B), dim3(BINV_BLOCK), st, B);
     launch_l0_lines(B, st);
     return;
   }

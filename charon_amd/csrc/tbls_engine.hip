@@ -142,6 +142,7 @@ struct tbg_ctx {
   uint32_t fb_window = TBG_FB_WINDOW;  // fallback line buffer positions per pass (tbg_config.fb_window)
   uint32_t sgb_mode = TBG_SGB_AUTO;    // batched subgroup test (tbg_config.subgroup_batch)
   uint32_t express_max = TBG_EXPRESS_PARTIALS;  // batches up to this many partials prefer the express slot
+  uint32_t l0_duty_partials = TBG_L0_DUTY_PARTIALS;  // fused level 0: P_d per duty from this many partials (tbg_config.l0_duty_partials)
   uint32_t n_simd = 1024;  // SIMDs of the device (CUs x 4): the level-0 shape rule's unit (l0_shape)
   // host-side work of the submit / collect calls (tbg_host_stats): [submits,
   // partials submitted, pack ns, enqueue ns, collects, partials collected,
@@ -258,6 +259,7 @@ int tbg_init(const tbg_config* cfg, tbg_ctx** out) {
   if (cfg && cfg->subgroup_batch > TBG_SGB_OFF) { delete c; return TBG_E_INVALID_ARG; }
   if (cfg) c->sgb_mode = cfg->subgroup_batch;
   if (cfg && cfg->express_partials) c->express_max = cfg->express_partials;
+  if (cfg && cfg->l0_duty_partials) c->l0_duty_partials = cfg->l0_duty_partials;
   if (hipSetDevice(dev) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&c->retire_ev, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->keys_ready, hipEventDisableTiming) != hipSuccess) {
@@ -1117,6 +1119,7 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   B.sgb_t = (G2J*)(dw + w_sgt);
   B.l0f_sum = (G2J*)(dw + w_l0fsum);
   B.l0f_u = (uint32_t*)(dw + w_l0fu);
+  B.l0_duty_partials = c->l0_duty_partials;
   B.agg_acc = (G2J*)(dw + w_aacc);
   B.agg_list = (uint32_t*)(dw + w_alist);
 

@@ -199,6 +199,7 @@ struct DevBatch {
   G2J* l0f_sum;           // [l0f_sum_entries] chunk sums of the Q_k columns and of T (k_l0f_reduce), then
                           // the L0F_COLS column totals (k_l0f_fold)
   uint32_t* l0f_u;        // [n_partials][4] the digits u_j of the fused r_i (k_sgb_sort -> k_rlc_g1_l0)
+  uint32_t l0_duty_partials;   // fused launches of at least this many partials form P_d per duty (l0_per_duty below)
   // recombination (k_aggregate.hip)
   G2J* agg_acc;           // [n_duties] integer-coefficient sums awaiting [1/D] (listed duties only)
   uint32_t* agg_list;     // [n_duties] duties whose Lagrange denominator D > 1
@@ -298,6 +299,17 @@ TBG_HD size_t sgb_q_slot(const DevBatch& B, uint32_t g, uint32_t k) {
 TBG_HD bool l0_fused(const DevBatch& B) {
   return TBG_PK_W2 && B.rlc_batch && B.rlc_group && B.sgb && B.n_partials;  // (the key products use the window table)
 }
+// The fused level 0's key side (k_rlc_g1_l0, k_msm.hip) runs one lane per
+// DUTY -- P_d in Straus' joint form, the 18 doublings once per duty
+// (bls_rlc.h rlc_duty_keys_l0f), affine P_d written by the same kernel -- in
+// launches of at least l0_duty_partials partials.  Smaller launches keep one lane per
+// partial and k_rlc_duty_sum<DSUM_L0_P>: with few waves the kernel's time is
+// one lane's chain, and the duty's chain is about three times the partial's
+// (tbg_config.l0_duty_partials, default TBG_L0_DUTY_PARTIALS).
+// The saving grows with the candidates of the launch and the cost with its
+// few, long waves, so the rule counts partials (config 3: 100k duties of ten).
+// A replayed prefix decides from its own partials.
+TBG_HD bool l0_per_duty(const DevBatch& B) { return l0_fused(B) && B.n_partials >= B.l0_duty_partials; }
 constexpr uint32_t SGB_T_PER = 32;  // candidates per slice of T (no longer a chain than a bucket slice's ~40)
 TBG_HD uint32_t sgb_t_slices(uint32_t m) { return m / SGB_T_PER; }  // (m: a power of two >= SGB_M_MIN = 64)
 constexpr uint32_t L0F_COLS = SGB_K + 1;        // the 18 sums over the groups of Q_k, then T

@@ -133,7 +133,15 @@ typedef struct {
                            * batch's ~50 short kernels then dispatch ahead of the
                            * throughput launches' workgroups): 0 -> TBG_EXPRESS_PARTIALS,
                            * TBG_EXPRESS_OFF -> no express slot                        */
+  uint32_t l0_duty_partials;   /* level 0 with the batched subgroup test on: device batches
+                           * of at least this many partials form each duty's key sum in
+                           * one pass, one lane per duty; smaller ones keep one lane
+                           * per partial (few waves: the shorter chain wins).  Same
+                           * results either way.  0 -> TBG_L0_DUTY_PARTIALS, 1 -> always,
+                           * TBG_L0_DUTY_NEVER -> never                                */
 } tbg_config;
+#define TBG_L0_DUTY_PARTIALS 600000u
+#define TBG_L0_DUTY_NEVER 0xFFFFFFFFu
 #define TBG_EXPRESS_PARTIALS 4096u
 #define TBG_EXPRESS_OFF 0xFFFFFFFFu
 #define TBG_SGB_AUTO 0

@@ -18,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 SRC = os.path.join(ROOT, "tests", "hostcheck", "hostcheck.cpp")
 LIB = os.path.join(ROOT, "tests", "hostcheck", "libhostcheck_count.so")
+L0_DUTY_PARTIALS = 600000  # include/tbls_gpu.h TBG_L0_DUTY_PARTIALS
 
 
 def main():
@@ -190,9 +191,37 @@ def main():
     l0f_per_launch = l0f_reduce + l0f_horner + lines_h + s_quad + final1
     sgb_bucket_t = sgb_bucket + madd
     decode_sgb_fused = decode_sgb + madd
-    l0f_partial = l0f_g1  # (no bucket additions: the signature side is the subgroup test's)
-    unit_3of4_l0 = (4 * decode_sgb_fused + hash_ + lines_h + 4 * l0f_partial + duty_sum_p4 + l0_per_group / G + agg
-                    + l0f_per_launch / launch_dvs)
+    # Per-duty key side (round 11; bls_rlc.h rlc_duty_keys_l0f, k_rlc_g1_l0 one
+    # lane per duty in launches of at least l0_duty_partials partials): P_d in
+    # Straus' joint form, the 18 doublings once per duty, and the affine
+    # conversion k_rlc_duty_sum<DSUM_L0_P> ran.  Probes: tests/l0straus/
+    # l0straus_host.cpp built with TBG_COUNT_OPS, four distinct keys and the
+    # digit sets above (7-of-10: ten candidates, keys repeating with other digits).
+    ssrc = os.path.join(ROOT, "tests", "l0straus", "l0straus_host.cpp")
+    slib_path = os.path.join(ROOT, "tests", "l0straus", "libl0straus_count.so")
+    subprocess.check_call(["/opt/rocm/llvm/bin/clang++", "-O1", "-std=c++17", "-fPIC", "-shared", "-DTBG_COUNT_OPS",
+                           "-Wno-pass-failed", ssrc, "-o", slib_path])
+    slib = ctypes.CDLL(slib_path)
+    slib.ls_count_get.restype = ctypes.c_ulonglong
+    assert slib.ls_probe_setup(b"".join(pks), len(pks)) == 0
+
+    def duty_probe(fn, n):
+        pid = (ctypes.c_uint32 * n)(*[k % len(pks) for k in range(n)])
+        c18 = (ctypes.c_int32 * (18 * n))(*[digit_sets[k % 3][(j + k // 3) % 18] for k in range(n) for j in range(18)])
+        u4 = (ctypes.c_uint32 * (4 * n))()
+        slib.ls_digits(c18, n, u4)
+        slib.ls_count_reset()
+        assert fn(pid, u4, n) == 0
+        return slib.ls_count_get()
+
+    l0s_duty4, l0s_partials4 = duty_probe(slib.ls_probe_duty, 4), duty_probe(slib.ls_probe_partials, 4)
+    l0s_duty10, l0s_partials10 = duty_probe(slib.ls_probe_duty, 10), duty_probe(slib.ls_probe_partials, 10)
+    l0s_to_affine = duty_sum_p4 - (l0s_partials4 - 4 * l0f_g1)  # k_rlc_duty_sum<DSUM_L0_P> less its three additions
+    l0f_partial = l0f_g1  # per-partial form (launches below l0_duty_partials): its key product; P_d by k_rlc_duty_sum
+    l0f_duty4 = l0s_duty4 + l0s_to_affine  # per-duty form: k_rlc_g1_l0 whole
+    unit_3of4_l0_per_partial = (4 * decode_sgb_fused + hash_ + lines_h + 4 * l0f_partial + duty_sum_p4 + l0_per_group / G
+                                + agg + l0f_per_launch / launch_dvs)
+    unit_3of4_l0 = unit_3of4_l0_per_partial - (4 * l0f_partial + duty_sum_p4) + l0f_duty4
     # every candidate but the first of each group is randomised: (4 G - 1) / G per duty
     unit_3of4_rlc = (4 * decode + hash_ + lines_h + (4 * G - 1) / G * rlc_partial + duty_sum4 + group_lines8 / G
                      + rlc_check_per_group / G + agg)
@@ -215,6 +244,11 @@ def main():
                  "unit_3of4_l0": round(unit_3of4_l0), "l0_launch_dvs": launch_dvs,
                  "unit_3of4_l0_bucket_msm": round(unit_3of4_l0_msm),
                  "l0f_partial": round(l0f_partial), "l0f_key_product": round(l0f_g1), "l0f_horner": l0f_horner,
+                 "l0f_duty_4": round(l0f_duty4), "l0f_duty_4_per_partial_form": round(4 * l0f_partial + duty_sum_p4),
+                 "l0f_duty_10_jacobian": l0s_duty10, "l0f_duty_10_jacobian_per_partial_form": l0s_partials10,
+                 "l0f_duty_4_jacobian": l0s_duty4, "l0f_duty_4_jacobian_per_partial_form": l0s_partials4,
+                 "unit_3of4_l0_per_partial_form": round(unit_3of4_l0_per_partial),
+                 "l0_duty_partials": L0_DUTY_PARTIALS,  # unit_3of4_l0 holds from this many partials per launch
                  "l0f_per_launch": round(l0f_per_launch),
                  "unit_3of4_l0_subgroup_alone": round(unit_3of4_l0_alone),
                  "decode_sig_batched_subgroup": round(decode_sgb), "sgb_per_partial": round(sgb_per_partial),
@@ -249,7 +283,14 @@ def main():
             "k_hash_clear_fin": {"per": "message", "mads": round(k_clear_fin)},
             "k_hash_affine": {"per": "message", "mads": round(k_g2_aff)},
             "k_lines_h": {"per": "message", "mads": round(lines_h)},
-            "k_rlc_g1_l0": {"per": "partial", "mads": round(l0f_g1)},  # (fused: 18 doublings + 18 additions)
+            # fused, one lane per duty (3-of-4 with four candidates): 18 doublings + 70 additions + the conversion.
+            # This prices launches of at least TBG_L0_DUTY_PARTIALS partials -- bench.py's per-kernel pass
+            # profiles a 16-batch launch, 640,000 partials.  A smaller launch (the driver shape's 7 + 7 + 6
+            # batches, config 4, a lone batch) runs k_rlc_g1_l0_per_partial and k_rlc_duty_sum<DSUM_L0_P>:
+            # price its kernel with those two entries and its unit with unit_3of4_l0_per_partial_form.
+            "k_rlc_g1_l0": {"per": "duty", "mads": round(l0f_duty4), "from_partials_per_launch": L0_DUTY_PARTIALS},
+            "k_rlc_g1_l0_per_partial": {"per": "partial", "mads": round(l0f_g1),
+                                        "below_partials_per_launch": L0_DUTY_PARTIALS},
             "k_l0f_reduce": {"per": "launch", "mads": round(l0f_reduce)},
             "k_l0f_horner": {"per": "launch", "mads": l0f_horner},
             # without the batched subgroup test: the bucket MSM (k_rlc_g1_l0 then costs k_rlc_g1_l0_msm)
