@@ -60,8 +60,9 @@ def is_stale():
 # kernels' VGPRs (k_sgb_sort 66 -> 119: 7 -> 4 waves) and the SSWU spills,
 # and lost at 20 steps although every big kernel ran faster alone.
 _ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
+# k_l0msg.hip holds k_miller_hex<MILLER_L0>'s body per message slot and takes that unit's flags.
 UNIT_FLAGS: dict = {u: _ILP for u in ("k_decode.hip", "k_miller_hex.hip", "k_verify.hip", "k_hash_clear.hip",
-                                       "k_aggregate.hip")}
+                                       "k_aggregate.hip", "k_l0msg.hip")}
 
 
 def build(force: bool = False, verbose: bool = False, jobs: int = 0, defines=(), out: str | None = None,
@@ -209,6 +210,7 @@ class TbgConfig(ctypes.Structure):
         ("subgroup_batch", ctypes.c_uint32),
         ("express_partials", ctypes.c_uint32),
         ("l0_duty_partials", ctypes.c_uint32),
+        ("l0_msg_share", ctypes.c_uint32),
     ]
 
 
@@ -239,6 +241,7 @@ SIGNATURES = {
     "tbg_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "tbg_fetch_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     "tbg_fetch_level0": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "tbg_fetch_level0_msgs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     "tbg_fetch_fallback": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     "tbg_fetch_subgroup": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
     "tbg_fetch_subgroup_schedule": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),

@@ -909,6 +909,8 @@ void launch_rlc_prepare(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff
     else launch_l0_msm(B, st);
     // (a per-duty key side has written P_d and dv_state itself: k_rlc_g1_l0)
     if (!l0_per_duty(B)) TBG_KLAUNCH(k_rlc_duty_sum<DSUM_L0_P>, duty_grid(B), dim3(BINV_BLOCK), st, B);
+    // shared messages: one key sum Q_m per distinct message (k_l0msg.hip)
+    if (l0_by_msg(B)) launch_l0m_sums(B, st);
     launch_l0_lines(B, st);
     return;
   }
@@ -975,9 +977,17 @@ void launch_rlc_check(const DevBatch& B0, const G1A* pk_aff, const G1A* xpk_aff,
     // SIMD, k_miller_hex.hip; the trio form measured 16.2 vs 15.2 ms, round 3)
     if (B.rlc_batch) {
       // level 0: the P chunks (kept for the group levels) and S, one product
-      launch_l0_miller_hex(B, st);
-      TBG_KLAUNCH(k_l0_fold, grid_for(hex_threads(n_groups)), dim3(kBlock), st, B);
-      uint32_t in = 0, n = n_groups, out = n_groups;
+      // (by message, l0_by_msg: Q_m against H(m) per message slot, the products of
+      // ceil(n_msgs / G) groups -- a fused launch, so nothing below reuses them)
+      const bool by_msg = l0_by_msg(B);
+      if (by_msg) {
+        launch_l0m_miller(B, st);
+      } else {
+        launch_l0_miller_hex(B, st);
+        TBG_KLAUNCH(k_l0_fold, grid_for(hex_threads(n_groups)), dim3(kBlock), st, B);
+      }
+      const uint32_t n_l0 = by_msg ? l0m_groups(B) : n_groups;
+      uint32_t in = 0, n = n_l0, out = n_l0;
       while (n > L0_TREE_FAN) {
         const uint32_t m = (n + L0_TREE_FAN - 1) / L0_TREE_FAN;
         TBG_KLAUNCH(k_l0_tree, grid_for(hex_threads(m)), dim3(kBlock), st, B, in, n, out);

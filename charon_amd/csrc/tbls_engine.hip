@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 #include "tbls_launch.h"
+#include "bls_l0msg.h"
 #include "bls_lines.h"
 
 using namespace tbg;
@@ -73,6 +74,9 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 struct Part {
   tbg_ticket ticket = 0;
   uint32_t d0 = 0, nd = 0, p0 = 0, np = 0, m0 = 0, nm = 0;
+  // level 0 by message (bls_l0msg.h): the chunks of the messages up to this part's
+  // last, and the largest message's chunks among them -- a replayed prefix's own plan
+  uint32_t ch1 = 0, maxch = 0;
   bool pending = false;     // not collected yet
   bool collecting = false;  // a blocking tbg_collect waits on the slot outside the context mutex
 };
@@ -143,6 +147,7 @@ struct tbg_ctx {
   uint32_t sgb_mode = TBG_SGB_AUTO;    // batched subgroup test (tbg_config.subgroup_batch)
   uint32_t express_max = TBG_EXPRESS_PARTIALS;  // batches up to this many partials prefer the express slot
   uint32_t l0_duty_partials = TBG_L0_DUTY_PARTIALS;  // fused level 0: P_d per duty from this many partials (tbg_config.l0_duty_partials)
+  uint32_t l0_msg_share = TBG_L0_MSG_SHARE;  // fused level 0: per message from this many duties per message (tbg_config.l0_msg_share)
   uint32_t n_simd = 1024;  // SIMDs of the device (CUs x 4): the level-0 shape rule's unit (l0_shape)
   // host-side work of the submit / collect calls (tbg_host_stats): [submits,
   // partials submitted, pack ns, enqueue ns, collects, partials collected,
@@ -260,6 +265,7 @@ int tbg_init(const tbg_config* cfg, tbg_ctx** out) {
   if (cfg) c->sgb_mode = cfg->subgroup_batch;
   if (cfg && cfg->express_partials) c->express_max = cfg->express_partials;
   if (cfg && cfg->l0_duty_partials) c->l0_duty_partials = cfg->l0_duty_partials;
+  if (cfg && cfg->l0_msg_share) c->l0_msg_share = cfg->l0_msg_share;
   if (hipSetDevice(dev) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&c->retire_ev, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->keys_ready, hipEventDisableTiming) != hipSuccess) {
@@ -766,6 +772,29 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   size_t o_ids = sec(np);
   size_t o_pk = sec(4ull * np);
   size_t o_dset = sec(set_first ? 4ull * nd : 0);
+  // Level 0 by message (bls_l0msg.h): the duties sorted by message and the
+  // chunk plan, packed with the inputs.  Reserved whenever a fused level 0
+  // may run with the knob on, whatever the launch's own duties per message:
+  // a replayed prefix decides from its own (l0_by_msg).  The work arena's
+  // sections follow below, once `fused` is known; this side is sized by the
+  // same conditions except the subgroup test's, which only shrink it.
+  // Nothing is reserved or sorted when no prefix of the caller batches
+  // reaches the share (one message per duty: the headline workload).
+  bool l0m_in = false;
+  if (verify && c->rlc_group != 0 && c->rlc_batch != TBG_RLC_L0_OFF && c->sgb_mode != TBG_SGB_OFF &&
+      c->l0_msg_share != TBG_L0_MSG_NEVER && np >= SGB_MIN_PARTIALS) {
+    uint64_t cd = 0, cm = 0;
+    for (uint32_t k = 0; k < n_batches; ++k) {
+      cd = set_first ? nd : cd + bs[k]->n_duties;
+      cm += bs[k]->n_msgs;
+      l0m_in = l0m_in || cm * c->l0_msg_share <= cd;
+    }
+  }
+  const size_t l0m_chunks = l0m_in ? (size_t)l0m_chunk_bound(nm, nd) : 0;
+  size_t o_mfirst = sec(l0m_in ? 4ull * (nm + 1) : 0);
+  size_t o_mduty = sec(l0m_in ? 4ull * nd : 0);
+  size_t o_cfirst = sec(l0m_in ? 4ull * (nm + 1) : 0);
+  size_t o_cmsg = sec(l0m_in ? 4ull * l0m_chunks : 0);
   size_t in_bytes = o;
   // ---- work/output arena ----
   o = 0;
@@ -856,6 +885,12 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   size_t w_sgt = sec(fused ? sizeof(G2J) * sgb_t_slices(sgb_m) * n_sg : 0);
   size_t w_l0fsum = sec(fused ? sizeof(G2J) * (size_t)l0f_sum_entries((uint32_t)n_sg, sgb_m) : 0);
   size_t w_l0fu = sec(fused ? 16ull * np : 0);
+  // level 0 by message: chunk sums and their member counts, Q_m, the messages' states
+  const bool l0m = fused && l0m_in;
+  size_t w_l0mpart = sec(l0m ? sizeof(G1J) * l0m_chunks : 0);
+  size_t w_l0mcnt = sec(l0m ? 4ull * l0m_chunks : 0);
+  size_t w_l0mq = sec(l0m ? sizeof(G1A) * (size_t)nm : 0);
+  size_t w_l0mst = sec(l0m ? 4ull * nm : 0);
   size_t w_aacc = sec(op != TBG_OP_VERIFY ? sizeof(G2J) * (size_t)nd : 0);
   size_t w_alist = sec(op != TBG_OP_VERIFY ? 4ull * nd : 0);
   size_t w_out = o;  // outputs are contiguous so one D2H copy brings them back
@@ -916,6 +951,10 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
       for (uint32_t m = 0; m < bnm; ++m) msg_off[M + m] = MB + b->msg_off[m];
       for (uint32_t d = 0; d < bnd; ++d) duty_msg[D + d] = M + b->duty_msg[d];
       memcpy(h + o_pk + 4ull * P, b->pubkey_ids, 4ull * bnp);
+      if (l0m) {  // this batch's duties by message (sections disjoint from the other batches')
+        std::vector<uint32_t> cursor(bnm);
+        l0m_sort_batch(duty_msg, D, bnd, M, bnm, (uint32_t*)(h + o_mfirst), (uint32_t*)(h + o_mduty), cursor.data());
+      }
     }
     for (uint32_t d = 0; d < bnd; ++d) {
       duty_first[D + d] = P + b->duty_first[d];
@@ -961,7 +1000,12 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
     }
     memset(thr, 0, 4ull * nd);
     parts[0].nd = nd;
+    if (l0m) {  // (the padded duties: a padding duty names message 0 and is never combined)
+      std::vector<uint32_t> cursor(nm);
+      l0m_sort_batch(duty_msg, 0, nd, 0, nm, (uint32_t*)(h + o_mfirst), (uint32_t*)(h + o_mduty), cursor.data());
+    }
   };
+  if (l0m) ((uint32_t*)(h + o_mfirst))[0] = 0;
   const uint32_t workers = (np >= (1u << 16) && n_batches > 1) ? std::min<uint32_t>(n_batches, 8) : 1;
   if (set_first) {
     pack_sets();
@@ -977,6 +1021,23 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   }
   duty_first[nd] = np;
   if (verify) msg_off[nm] = MB;
+  // Level 0 by message, the chunk plan (chunk -> message, message -> first
+  // chunk; the shape of SumPlan, k_sum.hip).  Invariant: the messages of
+  // caller batch j follow those of batch j - 1 and a message never spans
+  // caller batches (every batch brings its own), so batch j's duties, CSR
+  // rows and chunks all follow batch j - 1's -- the first n_msgs entries of
+  // msg_first / chunk_first, with the duties and chunks they cover, are a
+  // prefix's own plan (tbg_replay_plan n_parts; Part::ch1, ::maxch).
+  if (l0m) {
+    uint32_t nc = 0, largest = 0;
+    for (uint32_t k = 0; k < n_batches; ++k) {
+      const uint32_t big = l0m_chunk_plan((const uint32_t*)(h + o_mfirst), parts[k].m0, parts[k].nm,
+                                          (uint32_t*)(h + o_cfirst), (uint32_t*)(h + o_cmsg), &nc);
+      largest = std::max(largest, big);
+      parts[k].ch1 = nc;
+      parts[k].maxch = largest;
+    }
+  }
   const auto t_packed = std::chrono::steady_clock::now();
 
   lk.lock();
@@ -1120,6 +1181,17 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   B.l0f_sum = (G2J*)(dw + w_l0fsum);
   B.l0f_u = (uint32_t*)(dw + w_l0fu);
   B.l0_duty_partials = c->l0_duty_partials;
+  B.l0_msg_share = l0m ? c->l0_msg_share : TBG_L0_MSG_NEVER;  // (no plan: never by message)
+  B.l0m_n_chunks = l0m ? parts[n_batches - 1].ch1 : 0;
+  B.l0m_max_chunks = l0m ? parts[n_batches - 1].maxch : 0;
+  B.msg_first = (const uint32_t*)(di + o_mfirst);
+  B.msg_duty = (const uint32_t*)(di + o_mduty);
+  B.l0m_chunk_first = (const uint32_t*)(di + o_cfirst);
+  B.l0m_chunk_msg = (const uint32_t*)(di + o_cmsg);
+  B.l0m_part = (G1J*)(dw + w_l0mpart);
+  B.l0m_cnt = (uint32_t*)(dw + w_l0mcnt);
+  B.l0m_q = (G1A*)(dw + w_l0mq);
+  B.l0m_state = (int32_t*)(dw + w_l0mst);
   B.agg_acc = (G2J*)(dw + w_aacc);
   B.agg_list = (uint32_t*)(dw + w_alist);
 
@@ -1310,6 +1382,8 @@ int tbg_replay_plan(tbg_ctx* c, const tbg_ticket* tickets, const uint32_t* n_par
       B.n_duties = last.d0 + last.nd;
       B.n_partials = last.p0 + last.np;
       B.n_msgs = last.m0 + last.nm;
+      B.l0m_n_chunks = last.ch1;  // (the prefix's own plan, see submit_impl)
+      B.l0m_max_chunks = last.maxch;
     }
     bs[k] = B;
   }
@@ -1562,6 +1636,22 @@ int tbg_slot_bytes(tbg_ctx* c, tbg_ticket t, uint64_t* device_bytes, uint64_t* p
   if (!s) return TBG_E_TICKET;
   *device_bytes = (uint64_t)s->d_in_cap + (uint64_t)s->d_work_cap;
   *pinned_bytes = (uint64_t)s->h_in_cap + (uint64_t)s->h_out_cap;
+  return TBG_OK;
+}
+
+int tbg_fetch_level0_msgs(tbg_ctx* c, tbg_ticket t, uint32_t* out2) {
+  if (!c || !out2) return TBG_E_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(c->mu);
+  Slot* s = find_ticket(c, t, false, nullptr);
+  if (!s) return TBG_E_TICKET;
+  // (the launch's own fields: launch_rlc_check took its path from the same ones)
+  const DevBatch& B = s->last;
+  out2[0] = out2[1] = 0;
+  if (s->op == TBG_OP_AGGREGATE || !B.rlc_batch || !B.rlc_group || !B.n_duties) return TBG_OK;
+  const bool by_msg = l0_by_msg(B);
+  const uint32_t n = by_msg ? B.n_msgs : B.n_duties;
+  out2[0] = by_msg ? 1u : 0u;
+  out2[1] = ((n + B.rlc_group - 1) / B.rlc_group) * ((B.rlc_group + B.rlc_chunk - 1) / B.rlc_chunk);
   return TBG_OK;
 }
 

@@ -200,6 +200,20 @@ struct DevBatch {
                           // the L0F_COLS column totals (k_l0f_fold)
   uint32_t* l0f_u;        // [n_partials][4] the digits u_j of the fused r_i (k_sgb_sort -> k_rlc_g1_l0)
   uint32_t l0_duty_partials;   // fused launches of at least this many partials form P_d per duty (l0_per_duty below)
+  // level 0 by message (l0_by_msg below; bls_l0msg.h, k_l0msg.hip): one G1 sum
+  // Q_m per distinct message, so the Miller kernel evaluates H(m)'s lines once
+  // per message.  The plan is packed by the host with the launch's inputs.
+  uint32_t l0_msg_share;       // fused launches with at least this many duties per message pair per message
+  uint32_t l0m_n_chunks;       // chunks of this launch's messages (a replayed prefix: its own count)
+  uint32_t l0m_max_chunks;     // chunks of its largest message (the fold's pass count, l0m_passes)
+  const uint32_t* msg_first;   // [n_msgs + 1] CSR offsets into msg_duty
+  const uint32_t* msg_duty;    // [n_duties] duties by message, ascending inside a message
+  const uint32_t* l0m_chunk_first;  // [n_msgs + 1] first chunk of each message
+  const uint32_t* l0m_chunk_msg;    // [l0m_chunk_bound] message of each chunk
+  G1J* l0m_part;               // [l0m_chunk_bound] chunk sums, folded in place
+  uint32_t* l0m_cnt;           // [l0m_chunk_bound] combined duties in each sum
+  G1A* l0m_q;                  // [n_msgs] Q_m = sum of the message's P_d (affine), stored as (-x, y)
+  int32_t* l0m_state;          // [n_msgs] L0M_* (bls_l0msg.h)
   // recombination (k_aggregate.hip)
   G2J* agg_acc;           // [n_duties] integer-coefficient sums awaiting [1/D] (listed duties only)
   uint32_t* agg_list;     // [n_duties] duties whose Lagrange denominator D > 1
@@ -310,6 +324,21 @@ TBG_HD bool l0_fused(const DevBatch& B) {
 // few, long waves, so the rule counts partials (config 3: 100k duties of ten).
 // A replayed prefix decides from its own partials.
 TBG_HD bool l0_per_duty(const DevBatch& B) { return l0_fused(B) && B.n_partials >= B.l0_duty_partials; }
+// Level 0 by message (bls_l0msg.h, k_l0msg.hip).  By bilinearity
+//   prod_(d: m_d = m) e(P_d, H(m)) = e(sum_d P_d, H(m)),
+// so a fused launch in which messages are shared pairs ONE key sum Q_m per
+// distinct message: the 68 line evaluations of H(m) run once per message
+// instead of once per duty, against one mixed G1 addition per merged duty.
+// Fused launches only: a failed or void fused level 0 keeps nothing (the P
+// chunks are formed again with the classic scalars, launch_rlc_check), so no
+// fallback level sees the merged products.  l0_msg_share is the least number
+// of duties per distinct message at which a launch merges
+// (tbg_config.l0_msg_share, default TBG_L0_MSG_SHARE).  Decided from the
+// launch's own fields: a replayed prefix from its own duties and messages, a
+// set launch from its padded duties, a tbg_multi shard per shard.
+TBG_HD bool l0_by_msg(const DevBatch& B) {
+  return l0_fused(B) && B.l0_msg_share != TBG_L0_MSG_NEVER && (uint64_t)B.n_msgs * B.l0_msg_share <= B.n_duties;
+}
 constexpr uint32_t SGB_T_PER = 32;  // candidates per slice of T (no longer a chain than a bucket slice's ~40)
 TBG_HD uint32_t sgb_t_slices(uint32_t m) { return m / SGB_T_PER; }  // (m: a power of two >= SGB_M_MIN = 64)
 constexpr uint32_t L0F_COLS = SGB_K + 1;        // the 18 sums over the groups of Q_k, then T
@@ -455,6 +484,13 @@ void launch_l0_fused_s(const DevBatch& B, hipStream_t st);
 void launch_l0_check(const DevBatch& B, hipStream_t st);
 // level 0's P-chunk and S Miller products on hexads (k_miller_hex.hip)
 void launch_l0_miller_hex(const DevBatch& B, hipStream_t st);
+// level 0 by message (k_l0msg.hip): the message sums Q_m (after P_d, in
+// launch_rlc_prepare), then one hexad per chunk of message slots, the S
+// hexad and the fold over the message groups into grp_f (launch_rlc_check);
+// l0m_groups: the values the product tree then takes
+void launch_l0m_sums(const DevBatch& B, hipStream_t st);
+void launch_l0m_miller(const DevBatch& B, hipStream_t st);
+inline uint32_t l0m_groups(const DevBatch& B) { return (B.n_msgs + B.rlc_group - 1) / B.rlc_group; }
 // level 1's P-chunk and group-S Miller products on hexads (k_miller_hex.hip)
 void launch_groups_miller_hex(const DevBatch& B, hipStream_t st);
 // after a level-0 failure: the groups' S Miller products only (k_miller_hex.hip)

@@ -33,6 +33,7 @@ SGB_AUTO, SGB_ON, SGB_OFF = 0, 1, 2           # tbg_config.subgroup_batch
 SGB_SCHEDULES = ("none", "classic", "paired")  # TBG_SGB_SCHED_* (tbg_fetch_subgroup_schedule)
 EXPRESS_OFF = 0xFFFFFFFF                        # tbg_config.express_partials: no express slot
 L0_DUTY_ALWAYS, L0_DUTY_NEVER = 1, 0xFFFFFFFF   # tbg_config.l0_duty_partials (0: TBG_L0_DUTY_PARTIALS)
+L0_MSG_ALWAYS, L0_MSG_NEVER = 1, 0xFFFFFFFF     # tbg_config.l0_msg_share (0: TBG_L0_MSG_SHARE duties per message)
 L0_NOT_RUN, L0_PASSED, L0_FAILED = 0, 1, 2     # tbg_fetch_level0
 HOST_STAT_KEYS = ["submits", "partials_submitted", "pack_ns", "enqueue_ns", "collects", "partials_collected",
                   "gather_ns", "wait_ns"]
@@ -106,13 +107,14 @@ class Engine:
     def __init__(self, device: int = 0, slots: int = 3, verify_mode: int = VERIFY_RLC, rlc_group: int = 0,
                  rlc_seed: int = 0, rlc_chunk: int = 0, streams_per_slot: int = 0, rlc_batch: int = 0,
                  gident: int = GIDENT_OFF, fb_window: int = 0, subgroup_batch: int = SGB_AUTO,
-                 express_partials: int = 0, l0_duty_partials: int = 0):
+                 express_partials: int = 0, l0_duty_partials: int = 0, l0_msg_share: int = 0):
         self._lib = _native.load()
         cfg = _native.TbgConfig(device=device, max_partials=0, max_duties=0, max_msg_bytes=0, slots=slots,
                                 verify_mode=verify_mode, rlc_group=rlc_group, rlc_seed=rlc_seed,
                                 rlc_chunk=rlc_chunk, streams_per_slot=streams_per_slot, rlc_batch=rlc_batch,
                                 gident=gident, fb_window=fb_window, subgroup_batch=subgroup_batch,
-                                express_partials=express_partials, l0_duty_partials=l0_duty_partials)
+                                express_partials=express_partials, l0_duty_partials=l0_duty_partials,
+                                l0_msg_share=l0_msg_share)
         h = ctypes.c_void_p()
         rc = self._lib.tbg_init(ctypes.byref(cfg), ctypes.byref(h))
         self._check(rc, "tbg_init")
@@ -345,6 +347,14 @@ class Engine:
         self._check(self._lib.tbg_fetch_level0(self._h, ticket, ctypes.byref(st)), "tbg_fetch_level0")
         return st.value
 
+    def level0_msgs(self, ticket) -> dict:
+        """Level 0 of the batch's last run by message (tbg_fetch_level0_msgs):
+        "merged": it paired one key sum per distinct message (l0_msg_share);
+        "hexads": the P hexads its level-0 Miller kernel launched."""
+        out = np.zeros(2, dtype=np.uint32)
+        self._check(self._lib.tbg_fetch_level0_msgs(self._h, ticket, _ptr(out)), "tbg_fetch_level0_msgs")
+        return {"merged": bool(out[0]), "hexads": int(out[1])}
+
     def timings(self):
         ms = np.zeros(8, dtype=np.float32)
         self._check(self._lib.tbg_last_timings(self._h, _ptr(ms)), "tbg_last_timings")
@@ -410,12 +420,13 @@ class MultiEngine:
 
     def __init__(self, devices, slots: int = 3, verify_mode: int = VERIFY_RLC, rlc_group: int = 0, rlc_seed: int = 0,
                  rlc_chunk: int = 0, streams_per_slot: int = 0, rlc_batch: int = 0, gident: int = GIDENT_OFF,
-                 fb_window: int = 0, subgroup_batch: int = SGB_AUTO):
+                 fb_window: int = 0, subgroup_batch: int = SGB_AUTO, l0_msg_share: int = 0):
         self._lib = _native.load()
         cfg = _native.TbgConfig(device=0, max_partials=0, max_duties=0, max_msg_bytes=0, slots=slots,
                                 verify_mode=verify_mode, rlc_group=rlc_group, rlc_seed=rlc_seed,
                                 rlc_chunk=rlc_chunk, streams_per_slot=streams_per_slot, rlc_batch=rlc_batch,
-                                gident=gident, fb_window=fb_window, subgroup_batch=subgroup_batch)
+                                gident=gident, fb_window=fb_window, subgroup_batch=subgroup_batch,
+                                l0_msg_share=l0_msg_share)
         devs = np.ascontiguousarray(np.asarray(devices, dtype=np.int32))
         h = ctypes.c_void_p()
         rc = self._lib.tbg_multi_init(ctypes.byref(cfg), _ptr(devs), len(devs), ctypes.byref(h))

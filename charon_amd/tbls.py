@@ -191,6 +191,16 @@ def _raw(x, cls):
 
 
 # --------------------------------------------------------------------- batch API
+def _distinct_msgs(msgs):
+    """(distinct messages in first-seen order, item -> message index): equal
+    message bytes are sent -- and hashed to G2 -- once, and a fused level 0
+    pairs one key sum per distinct message (tbg_config.l0_msg_share).  A
+    parsigex set is N items over ONE root."""
+    index = {}
+    item_msg = np.fromiter((index.setdefault(m, len(index)) for m in msgs), dtype=np.uint32, count=len(msgs))
+    return list(index), item_msg
+
+
 def verify_batch(items, engine=None):
     """items: iterable of (pk, msg, sig).  Returns a list with True/False per
     item, or a TblsError for items whose encodings do not decode."""
@@ -202,10 +212,10 @@ def verify_batch(items, engine=None):
     present = [p for p in pks if p is not None]
     ids_present = iter(_pk_cache.ids_for(e, present))
     pk_ids = [next(ids_present) if p is not None else eng.NO_PUBKEY for p in pks]
-    msgs = [bytes(m) for _, m, _ in items]
+    msgs, item_msg = _distinct_msgs([bytes(m) for _, m, _ in items])
     sigs = b"".join(_raw(s, Signature) for _, _, s in items)
     n = len(items)
-    res = e.run(eng.OP_VERIFY, np.arange(n + 1), sigs, np.zeros(n, np.uint8), msgs=msgs, duty_msg=np.arange(n),
+    res = e.run(eng.OP_VERIFY, np.arange(n + 1), sigs, np.zeros(n, np.uint8), msgs=msgs, duty_msg=item_msg,
                 pubkey_ids=pk_ids)
     out = []
     for st in res.partial_status.tolist():
@@ -235,11 +245,11 @@ def verify_sets_batch(sets, engine=None):
     present = [p for p in pks if p is not None]
     ids_present = iter(_pk_cache.ids_for(e, present))
     pk_ids = [next(ids_present) if p is not None else eng.NO_PUBKEY for p in pks]
-    msgs = [bytes(m) for _, m, _ in items]
+    msgs, item_msg = _distinct_msgs([bytes(m) for _, m, _ in items])
     sigs = b"".join(_raw(s, Signature) for _, _, s in items)
     n = len(items)
     set_first = np.concatenate([[0], np.cumsum([len(s) for s in sets])])
-    res = e.run_sets(set_first, np.arange(n + 1), sigs, np.zeros(n, np.uint8), msgs=msgs, duty_msg=np.arange(n),
+    res = e.run_sets(set_first, np.arange(n + 1), sigs, np.zeros(n, np.uint8), msgs=msgs, duty_msg=item_msg,
                      pubkey_ids=pk_ids)
     return [st == eng.SS_VALID for st in res.set_status.tolist()]
 

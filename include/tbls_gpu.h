@@ -139,7 +139,16 @@ typedef struct {
                            * per partial (few waves: the shorter chain wins).  Same
                            * results either way.  0 -> TBG_L0_DUTY_PARTIALS, 1 -> always,
                            * TBG_L0_DUTY_NEVER -> never                                */
+  uint32_t l0_msg_share;  /* level 0 with the batched subgroup test on: the least number
+                           * of duties per distinct message (n_duties / n_msgs of the
+                           * device batch) at which level 0 sums the duties' key sums per
+                           * message and pairs ONE point with each H(m), instead of one
+                           * per duty.  Same results either way.  0 -> TBG_L0_MSG_SHARE,
+                           * 1 -> every such launch with n_msgs <= n_duties,
+                           * TBG_L0_MSG_NEVER -> never                                 */
 } tbg_config;
+#define TBG_L0_MSG_SHARE 2u
+#define TBG_L0_MSG_NEVER 0xFFFFFFFFu
 #define TBG_L0_DUTY_PARTIALS 600000u
 #define TBG_L0_DUTY_NEVER 0xFFFFFFFFu
 #define TBG_EXPRESS_PARTIALS 4096u
@@ -346,6 +355,11 @@ int tbg_fetch_shape(tbg_ctx* ctx, tbg_ticket ticket, uint32_t* out4);
  * partials collected, ns gathering (copy-out of statuses / aggregates and
  * the adaptive policies' counts), ns waiting for the device]. */
 int tbg_host_stats(tbg_ctx* ctx, uint64_t* out8, int reset);
+/* Level 0 of the ticket's last run by message: out2[0] = 1 if level 0 paired one
+ * key sum per distinct message (tbg_config.l0_msg_share), else 0; out2[1] = the
+ * P hexads (one per chunk of rlc_chunk pairs) its level-0 Miller kernel
+ * launched, 0 when level 0 did not run. */
+int tbg_fetch_level0_msgs(tbg_ctx* ctx, tbg_ticket ticket, uint32_t* out2);
 /* Footprint of the slot holding the ticket's batch: device bytes (input
  * arena + work arena) and pinned host bytes (staging both ways). */
 int tbg_slot_bytes(tbg_ctx* ctx, tbg_ticket ticket, uint64_t* device_bytes, uint64_t* pinned_bytes);

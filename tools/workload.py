@@ -8,7 +8,8 @@ tss.go:200-207).  Seeds are explicit so the CPU baseline and the GPU run use
 the same inputs.  make_batch's optional injection replaces a fraction of
 partials with a signature over a different message (a "wrong-message"
 partial); make_mixed_batch (config 5) injects every kind of invalid partial
-the reference rejects (INJECT_KINDS).
+the reference rejects (INJECT_KINDS); make_shared_batch is make_batch with a
+caller-given duty -> message map (duties that share signing roots).
 """
 from __future__ import annotations
 
@@ -208,4 +209,40 @@ def make_batch(engine, n_dv, t, n, seed, inject=0.0, load=None):
         msg_data=np.frombuffer(b"".join(msgs), dtype=np.uint8), msg_off=msg_off,
         duty_msg=np.arange(n_dv, dtype=np.uint32), threshold=np.full(n_dv, t, dtype=np.uint32),
         group_sig=group_sig, injected=injected, expect_ok=valid_per_dv >= t,
+        secrets=secrets, shares=shares, msgs=msgs, pk_first=int(first))
+
+
+def make_shared_batch(engine, n_dv, t, n, duty_msg, seed, n_msgs=None, load=None):
+    """make_batch with a caller-given duty -> message map: n_dv t-of-n DVs, DV d
+    signing root duty_msg[d] (every DV of a cluster signs the same root for a
+    randao, sync-message or selection duty; a committee's attesters share
+    theirs).  Partial signatures over the shared roots, group_sig from
+    engine.sign.  n_msgs (default max(duty_msg) + 1) may leave message
+    indices unused."""
+    rng = np.random.default_rng(seed)
+    duty_msg = np.ascontiguousarray(duty_msg, dtype=np.uint32)
+    assert len(duty_msg) == n_dv
+    n_msgs = int(duty_msg.max()) + 1 if n_msgs is None else n_msgs
+    assert n_msgs > int(duty_msg.max())
+    secrets = _scalars(rng, n_dv)
+    coeffs = _scalars(rng, n_dv * (t - 1))
+    shares = []
+    for d in range(n_dv):
+        shares += _shares(secrets[d], coeffs[d * (t - 1):(d + 1) * (t - 1)], range(1, n + 1))
+    msgs = [rng.bytes(32) for _ in range(n_msgs)]
+    n_p = n_dv * n
+    sk32 = b"".join(s.to_bytes(32, "big") for s in shares)
+    sigs = engine.sign(sk32, msgs, np.repeat(duty_msg, n).astype(np.uint32))
+    pubshares = engine.sk_to_pk(sk32)
+    first, st = (load or engine.load_pubkeys)(pubshares)
+    assert (st == 0).all()
+    group_sig = engine.sign(b"".join(s.to_bytes(32, "big") for s in secrets), msgs, duty_msg)
+    return ClusterBatch(
+        n_dv=n_dv, t=t, n=n,
+        duty_first=(np.arange(n_dv + 1, dtype=np.uint32) * n),
+        sigs=sigs, identifiers=np.tile(np.arange(1, n + 1, dtype=np.uint8), n_dv),
+        pubkey_ids=(first + np.arange(n_p)).astype(np.uint32), pubshares=pubshares,
+        msg_data=np.frombuffer(b"".join(msgs), dtype=np.uint8), msg_off=np.arange(n_msgs + 1, dtype=np.uint32) * 32,
+        duty_msg=duty_msg, threshold=np.full(n_dv, t, dtype=np.uint32),
+        group_sig=group_sig, injected=np.zeros(n_p, dtype=bool), expect_ok=np.ones(n_dv, dtype=bool),
         secrets=secrets, shares=shares, msgs=msgs, pk_first=int(first))
