@@ -31,6 +31,19 @@ __device__ __forceinline__ void sswu_in_store(G2J& s, const Fp2& u, const Fp2& x
 // The SSWU denominators' inversion is batched over the workgroup
 // (Montgomery's trick, bls_batchinv.h): one field inversion per BINV_BLOCK
 // messages instead of one per message.
+// hash_map_from_u: k_hash_map from message m's field elements on.  Every
+// thread of the workgroup calls it; a function of its own so that
+// tests/devcheck (devcheck_h2c.hip) can enter it with chosen u0, u1.
+__device__ __forceinline__ void hash_map_from_u(const DevBatch& B, uint32_t m, bool in, const Fp2& u0, const Fp2& u1) {
+  SswuPair w;
+  const Fp2 dd = sswu_pair_den(u0, u1, w);
+  const bool ok = in && !fp2_is_zero(dd);
+  const Fp2 di = block_batch_inv2<BINV_WAVES>(dd, ok);  // every thread of the workgroup
+  if (!in) return;
+  sswu_in_store(B.h_jac[m], u0, sswu_x1(fp2_mul(w.den[1], di)), ok);
+  sswu_in_store(B.h_jac[B.n_msgs + m], u1, sswu_x1(fp2_mul(w.den[0], di)), ok);
+}
+
 __global__ void __launch_bounds__(BINV_BLOCK, TBG_DECODE_WAVES) k_hash_map(DevBatch B) {
   const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = m < B.n_msgs;
@@ -39,13 +52,7 @@ __global__ void __launch_bounds__(BINV_BLOCK, TBG_DECODE_WAVES) k_hash_map(DevBa
     const uint32_t off = B.msg_off[m], len = B.msg_off[m + 1] - off;
     hash_to_field_fp2(B.msgs + off, len, u0, u1);
   }
-  SswuPair w;
-  const Fp2 dd = sswu_pair_den(u0, u1, w);
-  const bool ok = in && !fp2_is_zero(dd);
-  const Fp2 di = block_batch_inv2<BINV_WAVES>(dd, ok);  // every thread of the workgroup
-  if (!in) return;
-  sswu_in_store(B.h_jac[m], u0, sswu_x1(fp2_mul(w.den[1], di)), ok);
-  sswu_in_store(B.h_jac[B.n_msgs + m], u1, sswu_x1(fp2_mul(w.den[0], di)), ok);
+  hash_map_from_u(B, m, in, u0, u1);
 }
 
 // (SlotKeep, bls_tower.h: fp2_sqrt_or_z_in's g(x1) waits in the slot's Z)

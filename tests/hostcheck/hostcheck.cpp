@@ -1321,4 +1321,29 @@ int hc_g2_op_raw(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, ui
   }
   return 0;
 }
+// The host twins of tests/devcheck's hash-to-G2 entries (tests/edge_h2c.py):
+// both SSWU maps of one message from its field elements u0, u1 (28 raw words
+// each) as Jacobian points (84 words each) ...
+static Fp2 raw_fp2(const uint32_t* l) { return {raw_in(l), raw_in(l + NL)}; }
+static void raw_out(uint32_t* out, const Fp2& a) {
+  for (int i = 0; i < NL; ++i) {
+    out[i] = a.c0.l[i];
+    out[NL + i] = a.c1.l[i];
+  }
+}
+void hc_map_pair_u(const uint32_t* u0, const uint32_t* u1, uint32_t* q0, uint32_t* q1) {
+  G2J a, b;
+  map_to_curve_g2_pair(raw_fp2(u0), raw_fp2(u1), a, b);
+  raw_out(q0, a.X); raw_out(q0 + 2 * NL, a.Y); raw_out(q0 + 4 * NL, a.Z);
+  raw_out(q1, b.X); raw_out(q1 + 2 * NL, b.Y); raw_out(q1 + 4 * NL, b.Z);
+}
+// ... and the root of a or of Z a at k_hash_sswu's window width: bit 0 the
+// return value, bit 1 `sq`; root is zero where the function wrote none
+int hc_sqrt_or_z(const uint32_t* a, uint32_t* root) {
+  Fp2 r = fp2_zero();
+  bool sq = false;
+  const bool done = fp2_sqrt_or_z_in<SSWU_WIN>(raw_fp2(a), r, sq);
+  raw_out(root, r);
+  return (done ? 1 : 0) | (sq ? 2 : 0);
+}
 }
