@@ -7,6 +7,16 @@
 // G1 factor left out (l1', l4') and evaluated per public key as
 // l1 = l1' * (-x_pk), l4 = l4' * y_pk.  H(m) is shared by the n partials of a
 // DV, so its lines are computed once per message.
+//
+// A stored line is defined up to ONE non-zero Fp2 factor on its (l0, l1, l4):
+// every reader multiplies the lines into a Miller value that is then
+// final-exponentiated, and the final exponentiation maps Fp2* to 1.  The
+// signature side (g2_lines below, px_g2_lines, row_g2_lines) steps in Jacobian
+// coordinates, triple (3X^3 - 2Y^2, 3X^2 Z^2, 2Y Z^3) for a tangent; the H(m)
+// side (k_lines_h: bls_pair.h px_h_lines) steps in homogeneous projective
+// coordinates, triple (Y^2 - 3b'Z^2, 3X^2, 2YZ) -- the same line times a power
+// of Z and of 2, for 2 products + 7 squarings per tangent step instead of
+// 5 + 6.  The two families mix freely in one product.
 #pragma once
 #include "bls_pairing.h"
 

@@ -46,6 +46,10 @@ TBG_HD Fp pair_conj_lane(uint32_t par, const Fp& a) { return fp_select(par != 0,
 TBG_HD Fp pair_mul_xi_lane(uint32_t par, const Fp& a, const Fp& ap) {
   return fp_select(par != 0, fp_add(a, ap), fp_sub(a, ap));  // (a0 - a1) + (a0 + a1) u, lazy
 }
+// (the same with lazy limbs: for fp_mul_small / fp_reduce only; ap normalised)
+TBG_HD Fp pair_mul_xi_l_lane(uint32_t par, const Fp& a, const Fp& ap) {
+  return fp_select(par != 0, fp_add_l(a, ap), fp_sub_l(a, ap));
+}
 // 1 / a: the norm a0^2 + a1^2 is the same on both lanes.
 TBG_HD Fp pair_inv_lane(uint32_t par, const Fp& a, const Fp& ap) {
   const Fp t = fp_inv(fp_mul2(a, a, ap, ap));
@@ -289,6 +293,94 @@ TBG_HD LineG<F> miller_add_g(Jac<F>& T, const Aff<F>& Q, const Fp& nxP, const Fp
 TBG_HD Fp2 f_mulfp(const Fp2& a, const Fp& c) { return fp2_mul_fp(a, c); }
 TBG_HD Fp2p f_mulfp(const Fp2p& a, const Fp& c) { return rlc_mul_c(a, c); }
 
+// a (1 + u) with lazy limbs (value < a + 16p): for f_small / f_reduce only
+TBG_HD Fp2 f_mulxi_l(const Fp2& a) { return fp2_mul_xi(a); }
+TBG_HD Fp2p f_mulxi_l(const Fp2p& a) {
+  return {pair_mul_xi_l_lane(0, a.c0, a.c1), pair_mul_xi_l_lane(1, a.c1, a.c0)};
+}
+
+// The H(m) lines (k_lines_h): the same 68 lines from HOMOGENEOUS projective
+// steps (Costello, Lange, Naehrig, "Faster pairing computations on curves
+// with high-degree twists", a = 0), where the tangent's coefficients are
+// by-products of the doubling: 2 products + 7 squarings per tangent step
+// against the Jacobian step's 5 + 6.  Unevaluated form only (l1 to be
+// multiplied by -x_P, l4 by y_P, as miller_*_s<EVAL = false>).  A step's
+// (l0, l1, l4) is the Jacobian step's triple times ONE non-zero Fp2 factor
+// (a power of Z times a power of 2); the final exponentiation maps every Fp2
+// factor to 1 (p^2 - 1 divides (p^12 - 1) / r), so any pairing value formed
+// from these lines is the one formed from the others.  x = X / Z, y = Y / Z;
+// Z = 0 or Y = 0 never occurs on the doubling chain of a point of order r.
+// Every coefficient and coordinate leaves a step normalised and < 2p.
+template <class F> struct Prj { F X, Y, Z; };
+template <class F> TBG_HD Prj<F> prj_from_aff(const Aff<F>& a) { return {a.x, a.y, f_one<F>()}; }
+
+// Tangent at T, then T <- 2T.  With b' = 4 (1 + u):
+//   A = X^2, B = Y^2, C = Z^2, D = 3 b' C, E = (X + Y)^2 - A - B = 2XY,
+//   F = (Y + Z)^2 - B - C = 2YZ, G = 3D
+//   l4 = F, l1 = 3A, l0 = B - D   [Z^2 (2y y_P - 3x^2 x_P + y^2 - 3b')]
+//   X3 = E (B - G), Y3 = (B + G)^2 - 12 D^2, Z3 = 4 B F
+// in an order that retires X, then Y and Z, early (see miller_dbl_s).
+template <class F, class S>
+TBG_HD void hline_dbl_s(Prj<F>& T, S&& sink) {
+  const F A = f_sqr(T.X);
+  sink(1, f_reduce(f_add_l(f_add_l(A, A), A)));
+  const F B = f_sqr(T.Y);
+  const F E = f_sub_l(f_sqr(f_add(T.X, T.Y)), f_add(A, B));         // < 18p, lazy: a first operand
+  const F C = f_sqr(T.Z);
+  const F Fr = f_reduce(f_sub_l(f_sqr(f_add(T.Y, T.Z)), f_add(B, C)));
+  sink(2, Fr);
+  const F D = f_reduce(f_small(f_mulxi_l(C), 12));                  // 3 b' = 12 (1 + u); < 216p before
+  sink(0, f_reduce(f_sub_l(B, D)));
+  const F B2 = f_add_l(B, B);
+  const F Z3 = f_mul(f_add_l(B2, B2), Fr);                          // (limbs < 2^30: the first operand)
+  const F D2 = f_add(D, D);
+  const F G = f_add(D2, D);                                         // < 6p
+  const F X3 = f_mul(E, f_reduce(f_sub_l(B, G)));
+  const F S1 = f_sqr(f_add(B, G));
+  const F t = f_sqr(D2);                                            // 4 D^2
+  const F Y3 = f_reduce(f_sub_l(f_sub_l(f_sub_l(S1, t), t), t));    // < 50p, limbs < 2^31
+  T = {X3, Y3, Z3};
+}
+
+// Chord through T and the affine Q, then T <- T + Q (mixed, 11 products + 2
+// squarings):
+//   th = Y - y_Q Z, la = X - x_Q Z
+//   l4 = la, l1 = th, l0 = th x_Q - la y_Q   [Z (la' y_P - th' x_P + th' x_Q - la' y_Q)]
+//   C = th^2, D = la^2, E = la D, F = Z C, G = X D, H = E + F - 2G
+//   X3 = la H, Y3 = th (G - H) - E Y, Z3 = Z E
+template <class F, class S>
+TBG_HD void hline_add_s(Prj<F>& T, const Aff<F>& Q, S&& sink) {
+  const F th = f_reduce(f_sub_l(T.Y, f_mul(Q.y, T.Z)));
+  const F la = f_reduce(f_sub_l(T.X, f_mul(Q.x, T.Z)));
+  sink(2, la);
+  sink(1, th);
+  sink(0, f_reduce(f_sub_l(f_mul(th, Q.x), f_mul(la, Q.y))));
+  const F C = f_sqr(th);
+  const F D = f_sqr(la);
+  const F E = f_mul(la, D);
+  const F Fv = f_mul(T.Z, C);
+  const F G = f_mul(T.X, D);
+  const F H = f_reduce(f_sub_l(f_add_l(E, Fv), f_add(G, G)));
+  const F Z3 = f_mul(T.Z, E);
+  const F X3 = f_mul(la, H);
+  const F Y3 = f_reduce(f_sub_l(f_mul(f_sub_l(G, H), th), f_mul(E, T.Y)));
+  T = {X3, Y3, Z3};
+}
+
+template <class F>
+TBG_HD LineG<F> hline_dbl_g(Prj<F>& T) {
+  LineG<F> l;
+  hline_dbl_s(T, [&](int k, const F& v) { (k == 0 ? l.l0 : k == 1 ? l.l1 : l.l4) = v; });
+  return l;
+}
+
+template <class F>
+TBG_HD LineG<F> hline_add_g(Prj<F>& T, const Aff<F>& Q) {
+  LineG<F> l;
+  hline_add_s(T, Q, [&](int k, const F& v) { (k == 0 ? l.l0 : k == 1 ? l.l1 : l.l4) = v; });
+  return l;
+}
+
 // psi(a) == [x] a == -[|x|] a for an affine point on E2 (Scott), written for
 // any Fp2 representation F with the f_* / f_conj / f_mulc overloads: the lane
 // pair (Fp2x, device) and its host emulation (Fp2p).  Same schedule as
@@ -358,6 +450,7 @@ TBG_DEV Fp2x px_mul_const(const Fp2x& a, const Fp2Const& c) {
 }
 TBG_DEV Fp2x rlc_mul_c(const Fp2x& a, const Fp& c) { return {fp_mul(a.v, c)}; }  // Fp scalar: component-wise
 TBG_DEV Fp2x f_mulfp(const Fp2x& a, const Fp& c) { return {fp_mul(a.v, c)}; }
+TBG_DEV Fp2x f_mulxi_l(const Fp2x& a) { return {pair_mul_xi_l_lane(pair_par(), a.v, pair_xch(a.v))}; }
 TBG_DEV Fp2x f_conj(const Fp2x& a) { return px_conj(a); }
 TBG_DEV Fp2x f_mulc(const Fp2x& a, const Fp2Const& c) { return px_mul_const(a, c); }
 // (specialisations keep the primary templates' __host__ __device__; only the
@@ -406,6 +499,27 @@ TBG_DEV void px_g2_lines(const Aff<Fp2x>& Q, const Fp& nxP, const Fp& yP, uint32
     dst += LINE_WORDS;
     if ((X_ABS >> i) & 1) {
       miller_add_s<Fp2x, EVAL>(T, Q, nxP, yP, sink);
+      dst += LINE_WORDS;
+    }
+  }
+}
+
+// The 68 unevaluated lines of Q = H(m) in the same order and layout, from the
+// projective steps (hline_dbl_s / hline_add_s): each line is px_g2_lines<false>'s
+// times one non-zero Fp2 factor, which no final exponentiation sees.
+TBG_DEV void px_h_lines(const Aff<Fp2x>& Q, uint32_t* out) {
+  Prj<Fp2x> T = prj_from_aff(Q);
+  const uint32_t par = pair_par();
+  uint32_t* dst = out;
+  auto sink = [&](int k, const Fp2x& v) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i) dst[(2 * k + par) * NL + i] = v.v.l[i];
+  };
+  for (int i = 62; i >= 0; --i) {
+    hline_dbl_s(T, sink);
+    dst += LINE_WORDS;
+    if ((X_ABS >> i) & 1) {
+      hline_add_s(T, Q, sink);
       dst += LINE_WORDS;
     }
   }

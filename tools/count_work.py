@@ -45,13 +45,23 @@ def main():
     lib.hc_count_reset()
     assert lib.hc_stage_lines(sigs[0], msg, len(msg)) == 0
     lines_sig = lib.hc_count_get()
-    # H lines alone (per message): total of both minus the signature share
-    lib.hc_count_reset()
-    lib.hc_stage_lines(sigs[0], msg, len(msg))
-    # same schedule (68 steps on a G2 point) without folding P in: k_lines_h
-    # stores l1, l4 unevaluated (bls_pair.h EVAL = false), two Fp2 x Fp
-    # products (4 Fp products) fewer per line
-    lines_h = lines_sig - 68 * 4 * 392
+    # H lines (per message, k_lines_h): the projective steps of bls_pair.h
+    # (hline_dbl_s / hline_add_s, 2 products + 7 squarings per tangent step),
+    # l1 and l4 stored unevaluated.  Probe: tests/hlines/hlines_host.cpp built
+    # with TBG_COUNT_OPS, both lanes of the pair counted.  (The signature side
+    # keeps the Jacobian steps: lines_sig above.)
+    hsrc = os.path.join(ROOT, "tests", "hlines", "hlines_host.cpp")
+    hlib_path = os.path.join(ROOT, "tests", "hlines", "libhlines_count.so")
+    subprocess.check_call(["/opt/rocm/llvm/bin/clang++", "-O1", "-std=c++17", "-fPIC", "-shared", "-DTBG_COUNT_OPS",
+                           "-Wno-pass-failed", hsrc, "-o", hlib_path])
+    hlib = ctypes.CDLL(hlib_path)
+    hlib.hl_count_get.restype = ctypes.c_ulonglong
+    h_aff = ctypes.create_string_buffer(192)
+    assert hlib.hl_hash(msg, len(msg), h_aff) == 0
+    hlib.hl_count_reset()
+    hlib.hl_probe_lines(h_aff)
+    lines_h = hlib.hl_count_get()
+    lines_h_jacobian = lines_sig - 68 * 4 * 392  # the same 68 steps in Jacobian form with P left out (before)
     lib.hc_count_reset()
     assert lib.hc_stage_verify_quad(pks[0]) == 1
     verify_quad = lib.hc_count_get()
@@ -232,7 +242,7 @@ def main():
         "mads_per_fp_mul": 392,
         "rlc_schedule": {"group": G, "chunk": C},
         "mads": {"decode_sig": decode, "hash_to_g2": hash_, "lines_sig": lines_sig, "lines_h": lines_h,
-                 "verify_quad_item": verify_quad, "verify_item_single_lane": verify,
+                 "lines_h_jacobian_steps": lines_h_jacobian, "verify_quad_item": verify_quad, "verify_item_single_lane": verify,
                  "rlc_partial": rlc_partial, "rlc_duty_sum_4": duty_sum4, "rlc_group_lines": group_lines8,
                  "rlc_miller_chunk": chunk2, "rlc_miller_chunk_folded": chunk2f, "rlc_group_final": final4,
                  "rlc_check_per_group": rlc_check_per_group,
