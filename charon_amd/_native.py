@@ -211,6 +211,8 @@ class TbgConfig(ctypes.Structure):
         ("express_partials", ctypes.c_uint32),
         ("l0_duty_partials", ctypes.c_uint32),
         ("l0_msg_share", ctypes.c_uint32),
+        ("sgb_tri_partials", ctypes.c_uint32),
+        ("sgb_tri_m", ctypes.c_uint32),
     ]
 
 

@@ -47,6 +47,31 @@
 // wave iterations per member instead of 14.9 in index order (19.3 classic;
 // DESIGN section 4 has the table and the threshold).
 //
+// Triple schedule (groups larger than SGB_M: SGB_TRI_M = 16,384 members in
+// clean launches of at least tbg_config.sgb_tri_partials partials;
+// tbls_launch.h, bls_sgb.h).  The same step once more: for the triples
+// (3t, 3t + 1, 3t + 2), t = 0..5, member i goes into bucket
+// (a, b, c) = +-(c_i,3t, c_i,3t+1, c_i,3t+2), the first non-zero digit made
+// positive -- 1,098 buckets per triple, 6,588 per group, 6 x 2196/2197 = 6.0
+// mixed additions per member.  Such groups do not fit LDS, so the sort runs in
+// global memory:
+//   k_sgb_tri_count    one lane per member: digits, l0f_u, six bucket codes; the
+//                      group's counters by atomicAdd, whose result is the member's
+//                      place in its bucket
+//   k_sgb_tri_scan     one workgroup per group: counts -> offsets, buckets ranked
+//   k_sgb_tri_scatter  one lane per member: its entries to offset + place
+// k_sgb_bucket takes the ranked buckets as on the paired schedule, and
+//   k_sgb_tri_fold     pass 1: per triple P(a, b) = sum_c B(a, b, c) -- the paired
+//                      schedule's 84 buckets of (3t, 3t + 1) -- and the partial sums
+//                      E(v, a, +-) = sum_b B(a, b, +-v) of the third combination;
+//                      pass 2: the pair's R_a, D_v over P, and
+//                      D_v = sum_a (E(v, a, +) - E(v, a, -)) for the third
+// leaves the same 108 folded sums per group (chains of at most 14 terms;
+// ~2,350 additions per triple whatever the group's size, which is why only
+// large groups take it: DESIGN section 4).  The order inside a bucket follows
+// the atomics; the sums are group elements, so verdicts and bytes do not
+// depend on it.
+//
 // With the fused level 0 (bls_rlc.h, top) the same sums serve level 0's
 // S = sum r_i s_i: k_sgb_sort also stores the digits of r_i, k_sgb_bucket also
 // adds the group's unweighted sum T, and a failed group voids level 0.
@@ -66,6 +91,7 @@ namespace tbg {
 constexpr uint32_t kSgbSortBlock = TBG_SGB_SORT_BLOCK;  // threads per group's sort
 
 static_assert(SGBP_B == SGB_PB && SGBP_V == SGB_V && SGBP_SUMS * SGB_PAIRS == SGB_BUCKETS, "bls_sgb.h's pair layout");
+static_assert(SGBT_B == SGB_TB && SGBT_SUMS1 == SGB_TF1 && SGBT_SUMS2 * SGB_TRIPLES == SGB_BUCKETS, "bls_sgb.h's triple layout");
 static_assert((kSgbSortBlock & (kSgbSortBlock - 1)) == 0, "sgb_block_scan: a power of two");
 constexpr uint32_t SGB_RANK_KEYS = 256;  // bucket sizes 0..254 apart, larger ones together
 
@@ -224,18 +250,98 @@ __global__ void __launch_bounds__(kSgbSortBlock) k_sgb_sort(DevBatch B) {
   }
 }
 
+// ---- triple schedule: the sort in global memory (groups past SGB_M do not fit LDS) ----
+// k_sgb_tri_count, one lane per member: the digits once, l0f_u as k_sgb_sort
+// writes it, and per triple the member's bucket code.  The group's counters
+// are its sgb_off row (zeroed by the launcher); the count the atomicAdd
+// returns is the member's place in its bucket, kept in the code, so the
+// scatter needs no second round of atomics and no cursors.  (A workgroup's 256
+// members make 1,536 entries over 6,588 buckets: counting in LDS first would
+// merge next to nothing.)  The order inside a bucket follows the atomics and
+// differs from run to run; the sums are group elements, so verdicts and
+// bytes do not.
+__global__ void __launch_bounds__(kSgbSortBlock) k_sgb_tri_count(DevBatch B) {
+  const uint32_t i = blockIdx.x * kSgbSortBlock + threadIdx.x;
+  if (i >= B.n_partials) return;
+  const uint32_t g = i / B.sgb_m;
+  const bool ok = B.partial_status[i] == TBG_PS_NOT_VERIFIED;
+  int32_t c[SGB_K];
+  sgb_digits(B.sgb_seed, i, c);
+  if (l0_fused(B)) {  // (as in k_sgb_sort)
+    uint32_t u[4];
+    l0f_digits(c, u);
+    *(uint4*)(B.l0f_u + 4ull * i) = make_uint4(u[0], u[1], u[2], u[3]);
+  }
+  uint32_t* cnt = B.sgb_off + (size_t)(SGB_TBUCKETS + 1) * g;
+#pragma unroll
+  for (uint32_t t = 0; t < SGB_TRIPLES; ++t) {
+    uint32_t cd = ok ? sgb_tri_code(c[3 * t], c[3 * t + 1], c[3 * t + 2]) : SGBT_NONE;
+    if (cd != SGBT_NONE) cd |= atomicAdd(&cnt[t * SGB_TB + (cd & (SGBT_NEG - 1))], 1u) << 12;
+    B.sgb_code[(size_t)SGB_TRIPLES * i + t] = cd;
+  }
+}
+
+// k_sgb_tri_scan, one workgroup per group: its 6,588 counts -> offsets (in
+// place), and its buckets ranked by decreasing count for k_sgb_bucket (the
+// counting sort of the paired schedule, more keys)
+__global__ void __launch_bounds__(kSgbSortBlock) k_sgb_tri_scan(DevBatch B) {
+  __shared__ uint32_t cnt[SGB_TBUCKETS + 1];
+  __shared__ uint32_t hist[SGB_RANK_KEYS + 1];
+  __shared__ uint32_t tmp[kSgbSortBlock];
+  __shared__ uint8_t key[SGB_TBUCKETS];
+  const uint32_t g = blockIdx.x, t = threadIdx.x;
+  uint32_t* goff = B.sgb_off + (size_t)(SGB_TBUCKETS + 1) * g;
+  uint32_t* rank = B.sgb_rank + (size_t)SGB_TBUCKETS * g;
+  for (uint32_t b = t; b < SGB_RANK_KEYS; b += kSgbSortBlock) hist[b] = 0;
+  if (t == 0) B.sgb_bad[g] = 0;
+  __syncthreads();
+  for (uint32_t b = t; b < SGB_TBUCKETS; b += kSgbSortBlock) {  // larger buckets first
+    const uint32_t n = goff[b];
+    cnt[b] = n;
+    const uint32_t k = SGB_RANK_KEYS - 1 - min(n, SGB_RANK_KEYS - 1);
+    key[b] = (uint8_t)k;
+    atomicAdd(&hist[k], 1u);
+  }
+  __syncthreads();
+  sgb_block_scan<SGB_TBUCKETS>(cnt, tmp);
+  sgb_block_scan<SGB_RANK_KEYS>(hist, tmp);
+  for (uint32_t b = t; b <= SGB_TBUCKETS; b += kSgbSortBlock) {
+    goff[b] = cnt[b];
+    if (b < SGB_TBUCKETS) rank[atomicAdd(&hist[key[b]], 1u)] = b;  // (every rank 0..6587 once)
+  }
+}
+
+// k_sgb_tri_scatter, one lane per member: its (member, sign) entries, one per
+// triple, to the places k_sgb_tri_count drew
+__global__ void __launch_bounds__(kSgbSortBlock) k_sgb_tri_scatter(DevBatch B) {
+  const uint32_t i = blockIdx.x * kSgbSortBlock + threadIdx.x;
+  if (i >= B.n_partials) return;
+  const uint32_t m = B.sgb_m, g = i / m, li = i - g * m;
+  const uint32_t* goff = B.sgb_off + (size_t)(SGB_TBUCKETS + 1) * g;
+  uint32_t* ent = B.sgb_ent + (size_t)sgb_ent_stride(m) * g;
+#pragma unroll
+  for (uint32_t t = 0; t < SGB_TRIPLES; ++t) {
+    const uint32_t cd = B.sgb_code[(size_t)SGB_TRIPLES * i + t];
+    if (cd == SGBT_NONE) continue;
+    ent[goff[t * SGB_TB + (cd & (SGBT_NEG - 1))] + (cd >> 12)] = (li << 1) | ((cd / SGBT_NEG) & 1u);
+  }
+}
+
 // one lane pair per (group, bucket, slice) -- on the paired schedule per
 // (group, rank): the SGB_PRANK = 768 pairs of a group take its 756 buckets in
 // the order of k_sgb_sort's ranking, so the 32 pairs of a wave hold buckets
-// of near-equal length (the last 12 are idle); with the fused level 0 further
+// of near-equal length (the last 12 are idle), and on the triple schedule the
+// SGB_TRANK = 6,592 pairs its 6,588 buckets in the same way; with the fused level 0 further
 // pairs, one per (group, SGB_T_PER consecutive members), add the group's
 // unweighted sum T: one more bucket with coefficient +1 whose members are the
 // candidates at sort time (nothing changes a status between the two kernels)
 __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_bucket(DevBatch B, uint32_t n_sg, uint32_t n_t) {
   uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;  // both lanes of a pair take the same branches
   const uint32_t S = B.sgb_split, m = B.sgb_m;
-  const bool paired = sgb_paired(m);
-  const uint32_t per_g = paired ? SGB_PRANK : SGB_BUCKETS * S;
+  const bool triple = sgb_triple(m);
+  const bool paired = sgb_paired(m) || triple;  // (ranked buckets; grid-uniform)
+  const uint32_t n_rank = triple ? SGB_TBUCKETS : SGB_PBUCKETS;  // the ranked schedules' buckets per group
+  const uint32_t per_g = triple ? SGB_TRANK : paired ? SGB_PRANK : SGB_BUCKETS * S;
   // T's pairs: after the buckets' on the classic schedule; FIRST on the paired
   // one, whose bucket chains (~12 additions a wave, the last waves of a group
   // next to none) are shorter than T's 32 -- started last, T's waves were the
@@ -263,10 +369,10 @@ __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_bucket(DevBatch B, uint32_t n
   uint32_t e0, e1;
   size_t out;
   if (paired) {
-    const uint32_t r = w % SGB_PRANK;
-    if (r >= SGB_PBUCKETS) return;
-    const uint32_t b = B.sgb_rank[(size_t)SGB_PBUCKETS * g + r];
-    const uint32_t* goff = B.sgb_off + (size_t)(SGB_PBUCKETS + 1) * g;
+    const uint32_t r = w % per_g;
+    if (r >= n_rank) return;
+    const uint32_t b = B.sgb_rank[(size_t)n_rank * g + r];
+    const uint32_t* goff = B.sgb_off + (size_t)(n_rank + 1) * g;
     e0 = goff[b];
     e1 = goff[b + 1];
     out = (size_t)sgb_part_stride(m) * g + b;
@@ -346,6 +452,32 @@ __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_fold(DevBatch B, uint32_t n_s
   px_store(part[0], acc);
 }
 
+// Triple schedule's fold in two passes (bls_sgb.h sgb_tri_sum1_g, _sum2_g).
+// Pass 1, one lane pair per (group, triple, one of its 168 sums P, E): chains
+// of at most 13 bucket sums, stored after the group's bucket sums.  Pass 2,
+// one lane pair per (group, triple, one of its 18 sums R_a, D_v, D_v): chains
+// of 13 or 14 first-pass sums, stored in the layout of the classic
+// schedule's folded buckets.  Equal operands are redone as above.
+__device__ __noinline__ Jac<Fp2x> sgb_tri_sum_complete(const G2J* src, uint32_t j, uint32_t pass) {
+  bool unused = false;
+  auto ld = [&](uint32_t idx) { return px_load(src[idx]); };
+  return pass == 1 ? sgb_tri_sum1_g<Fp2x, false>(ld, j, unused) : sgb_tri_sum2_g<Fp2x, false>(ld, j, unused);
+}
+
+__global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_tri_fold(DevBatch B, uint32_t n_sg, uint32_t pass) {
+  const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;  // both lanes of a pair take the same branches
+  const uint32_t per_t = pass == 1 ? SGB_TF1 : SGBT_SUMS2, per_g = SGB_TRIPLES * per_t;
+  if (w >= n_sg * per_g) return;
+  const uint32_t g = w / per_g, t = (w % per_g) / per_t, j = w % per_t;
+  G2J* grp = B.sgb_part + (size_t)sgb_part_stride(B.sgb_m) * g;
+  const G2J* src = pass == 1 ? grp + (size_t)SGB_TB * t : grp + SGB_TBUCKETS + (size_t)SGB_TF1 * t;
+  auto ld = [&](uint32_t idx) { return px_load(src[idx]); };
+  bool exc = false;
+  Jac<Fp2x> acc = pass == 1 ? sgb_tri_sum1_g<Fp2x, true>(ld, j, exc) : sgb_tri_sum2_g<Fp2x, true>(ld, j, exc);
+  if (!pair_all(!exc)) acc = sgb_tri_sum_complete(src, j, pass);  // (pair-uniform)
+  px_store(grp[(pass == 1 ? SGB_TBUCKETS : SGB_TFOLD) + w % per_g], acc);
+}
+
 // one lane pair per (group, combination): Q_k = sum_v v B_v by running sums
 // from v = 6 down over the folded buckets, stored over the combination's
 // first bucket (only this pair reads those buckets)
@@ -357,7 +489,7 @@ __device__ __noinline__ Jac<Fp2x> sgb_combine_complete(const G2J* part, uint32_t
 __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_sgb_combine(DevBatch B, uint32_t n_sg) {
   const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;  // both lanes of a pair take the same branches
   if (w >= n_sg * SGB_K) return;
-  const uint32_t g = w / SGB_K, k = w % SGB_K, S = sgb_paired(B.sgb_m) ? 1u : B.sgb_split;
+  const uint32_t g = w / SGB_K, k = w % SGB_K, S = sgb_paired(B.sgb_m) || sgb_triple(B.sgb_m) ? 1u : B.sgb_split;
   G2J* part = B.sgb_part + sgb_q_slot(B, g, k);
   bool exc = false;
   Jac<Fp2x> q = sgb_running_sums_g<Fp2x, true>([&](uint32_t v) { return px_load(part[(size_t)v * S]); }, SGB_V, exc);
@@ -404,12 +536,26 @@ void launch_subgroup_batch(const DevBatch& B, hipStream_t st) {
   if (!B.sgb) return;
   const uint32_t n_sg = sgb_groups(B.n_partials, B.sgb_m);
   if (!n_sg) return;
-  TBG_KLAUNCH(k_sgb_sort, dim3(n_sg), dim3(kSgbSortBlock), st, B);
+  const bool triple = sgb_triple(B.sgb_m), paired = sgb_paired(B.sgb_m);
+  if (triple) {
+    const dim3 per_member((B.n_partials + kSgbSortBlock - 1) / kSgbSortBlock);
+    (void)hipMemsetAsync(B.sgb_off, 0, 4ull * (SGB_TBUCKETS + 1) * n_sg, st);  // k_sgb_tri_count's counters
+    TBG_KLAUNCH(k_sgb_tri_count, per_member, dim3(kSgbSortBlock), st, B);
+    TBG_KLAUNCH(k_sgb_tri_scan, dim3(n_sg), dim3(kSgbSortBlock), st, B);
+    TBG_KLAUNCH(k_sgb_tri_scatter, per_member, dim3(kSgbSortBlock), st, B);
+  } else {
+    TBG_KLAUNCH(k_sgb_sort, dim3(n_sg), dim3(kSgbSortBlock), st, B);
+  }
   const uint32_t n_t = l0_fused(B) ? sgb_t_slices(B.sgb_m) : 0u;  // the slices of T per group
-  const bool paired = sgb_paired(B.sgb_m);
-  const uint32_t per_g = paired ? SGB_PRANK : SGB_BUCKETS * B.sgb_split;  // k_sgb_bucket's lane pairs per group
+  // k_sgb_bucket's lane pairs per group
+  const uint32_t per_g = triple ? SGB_TRANK : paired ? SGB_PRANK : SGB_BUCKETS * B.sgb_split;
   TBG_KLAUNCH(k_sgb_bucket, grid_for(2 * n_sg * (per_g + n_t)), dim3(kBlock), st, B, n_sg, n_t);
-  if (paired || B.sgb_split > 1) TBG_KLAUNCH(k_sgb_fold, grid_for(2 * n_sg * SGB_BUCKETS), dim3(kBlock), st, B, n_sg);
+  if (triple) {
+    TBG_KLAUNCH(k_sgb_tri_fold, grid_for(2 * n_sg * SGB_TRIPLES * SGB_TF1), dim3(kBlock), st, B, n_sg, 1u);
+    TBG_KLAUNCH(k_sgb_tri_fold, grid_for(2 * n_sg * SGB_BUCKETS), dim3(kBlock), st, B, n_sg, 2u);
+  } else if (paired || B.sgb_split > 1) {
+    TBG_KLAUNCH(k_sgb_fold, grid_for(2 * n_sg * SGB_BUCKETS), dim3(kBlock), st, B, n_sg);
+  }
   TBG_KLAUNCH(k_sgb_combine, grid_for(2 * n_sg * SGB_K), dim3(kBlock), st, B, n_sg);
   TBG_KLAUNCH(k_sgb_test, grid_for(2 * n_sg * SGB_K), dim3(kBlock), st, B, n_sg);
 }

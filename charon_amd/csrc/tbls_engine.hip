@@ -109,6 +109,7 @@ struct Slot {
   tbg::DevBatch last{};        // the batch as its last run launched it (a replay's prefix and shape):
                                // what tbg_fetch_stats / _fallback / _shape / _subgroup describe
   size_t w_out = 0;
+  uint32_t sgb_m_small = 0;    // the group size of a prefix below sgb_tri_partials (its arena holds both layouts)
   // a set launch (tbg_submit_sets): its one part spans the padded device batch
   bool sets = false;
   uint32_t n_sets = 0;
@@ -148,6 +149,8 @@ struct tbg_ctx {
   uint32_t express_max = TBG_EXPRESS_PARTIALS;  // batches up to this many partials prefer the express slot
   uint32_t l0_duty_partials = TBG_L0_DUTY_PARTIALS;  // fused level 0: P_d per duty from this many partials (tbg_config.l0_duty_partials)
   uint32_t l0_msg_share = TBG_L0_MSG_SHARE;  // fused level 0: per message from this many duties per message (tbg_config.l0_msg_share)
+  uint32_t sgb_tri_partials = TBG_SGB_TRI_PARTIALS;  // batched subgroup test: triple schedule from this many partials (tbg_config.sgb_tri_partials)
+  uint32_t sgb_tri_m = SGB_TRI_M;                    // its group size (tbg_config.sgb_tri_m)
   uint32_t n_simd = 1024;  // SIMDs of the device (CUs x 4): the level-0 shape rule's unit (l0_shape)
   // host-side work of the submit / collect calls (tbg_host_stats): [submits,
   // partials submitted, pack ns, enqueue ns, collects, partials collected,
@@ -266,6 +269,12 @@ int tbg_init(const tbg_config* cfg, tbg_ctx** out) {
   if (cfg && cfg->express_partials) c->express_max = cfg->express_partials;
   if (cfg && cfg->l0_duty_partials) c->l0_duty_partials = cfg->l0_duty_partials;
   if (cfg && cfg->l0_msg_share) c->l0_msg_share = cfg->l0_msg_share;
+  if (cfg && cfg->sgb_tri_partials) c->sgb_tri_partials = cfg->sgb_tri_partials;
+  if (cfg && cfg->sgb_tri_m) c->sgb_tri_m = cfg->sgb_tri_m;
+  if (!sgb_triple(c->sgb_tri_m) || c->sgb_tri_m > SGB_TRI_M_MAX || (c->sgb_tri_m & (c->sgb_tri_m - 1))) {
+    delete c;
+    return TBG_E_INVALID_ARG;
+  }
   if (hipSetDevice(dev) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&c->retire_ev, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->keys_ready, hipEventDisableTiming) != hipSuccess) {
@@ -697,6 +706,31 @@ static bool sgb_plan(double rho, uint32_t& m) {
   return best < 0.95;
 }
 
+// The triple schedule (tbls_launch.h sgb_triple) in the same units.  Whether
+// its arithmetic pays at a launch's size is the threshold's business
+// (tbg_config.sgb_tri_partials, set from an A/B like l0_duty_partials): the
+// count model (tools/sgb_pair_model.py) has bucket
+// additions, ranked slots and reductions at 7.30 per member in groups of
+// 16,384 against the paired 11.66 at 1,024, so 0.55 x (1 - 7.30 / 11.66) =
+// 0.21 less per signature.  What the plan weighs is the term that grows with
+// the group: a failed group's members are tested alone, 1 - (1 - rho)^m of
+// them, against the same term at the size `m_small` that sgb_plan picked.
+// The triple schedule runs while that difference stays under the modelled
+// saving -- rho up to ~1.4e-5 at 16,384, the clean regime; any measurable
+// non-subgroup share falls back to the paired sizes exactly as before.
+static bool sgb_plan_triple(double rho, uint32_t m_small, uint32_t m_tri) {
+  const double r = std::min(rho, 1.0);
+  const double extra = std::pow(1.0 - r, (double)m_small) - std::pow(1.0 - r, (double)m_tri) +
+                       1.1 * (double)SGB_K * (1.0 / m_tri - 1.0 / m_small);
+  return extra < 0.55 * (1.0 - 7.30 / 11.66);
+}
+// The launch's group size: sgb_plan's, or the triple schedule's in a clean
+// launch of at least sgb_tri_partials partials.  (A replayed prefix asks
+// again with its own partial count.)
+static uint32_t sgb_group_size(const tbg_ctx* c, uint32_t np, uint32_t m_small, bool clean_tri) {
+  return clean_tri && np >= c->sgb_tri_partials ? c->sgb_tri_m : m_small;
+}
+
 // Device duties of a set launch at group size G: every non-empty set starts on
 // a multiple of G (the duties between are empty padding), so no level-1 group
 // holds duties of two sets.
@@ -862,13 +896,25 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   uint32_t sgb_m = SGB_M;
   const bool sgb = np >= SGB_MIN_PARTIALS && c->sgb_mode != TBG_SGB_OFF &&
                    (sgb_plan(c->nonsub_ema, sgb_m) || c->sgb_mode == TBG_SGB_ON);
-  const uint32_t sgb_split = sgb_split_for(sgb_m);
+  // A clean launch of at least sgb_tri_partials partials takes the triple
+  // schedule's large groups.  A replayed prefix below the threshold goes back
+  // to sgb_m_small, so such a launch's sections hold either layout.
+  const uint32_t sgb_m_small = sgb_m;
+  const bool sgb_tri_ok = sgb && sgb_plan_triple(c->nonsub_ema, sgb_m_small, c->sgb_tri_m);
+  sgb_m = sgb_group_size(c, np, sgb_m_small, sgb_tri_ok);
+  const bool sgb_tri = sgb_triple(sgb_m);
+  const uint32_t sgb_split = sgb_tri ? 1u : sgb_split_for(sgb_m);
   const size_t n_sg = sgb ? sgb_groups(np, sgb_m) : 0;
-  size_t w_sgoff = sec(4ull * sgb_off_stride(sgb_m) * n_sg);
-  size_t w_sgent = sec(4ull * sgb_ent_stride(sgb_m) * n_sg);
-  size_t w_sgpart = sec(sizeof(G2J) * sgb_part_stride(sgb_m) * n_sg);
-  size_t w_sgrank = sec(sgb_paired(sgb_m) ? 4ull * SGB_PBUCKETS * n_sg : 0);
-  size_t w_sgbad = sec(4ull * n_sg);
+  const size_t n_sg_small = sgb ? sgb_groups(np, sgb_m_small) : 0;  // (the most groups a prefix can have)
+  auto sgsec = [&](auto&& per_group) {  // a section of per_group(m) units per group, in either layout
+    return std::max<size_t>(per_group(sgb_m) * n_sg, sgb_tri ? per_group(sgb_m_small) * n_sg_small : 0);
+  };
+  size_t w_sgoff = sec(4ull * sgsec([](uint32_t m) { return (size_t)sgb_off_stride(m); }));
+  size_t w_sgent = sec(4ull * sgsec([](uint32_t m) { return (size_t)sgb_ent_stride(m); }));
+  size_t w_sgpart = sec(sizeof(G2J) * sgsec([](uint32_t m) { return (size_t)sgb_part_stride(m); }));
+  size_t w_sgrank = sec(4ull * sgsec([](uint32_t m) { return (size_t)sgb_rank_stride(m); }));
+  size_t w_sgcode = sec(sgb_tri ? 4ull * SGB_TRIPLES * np : 0);
+  size_t w_sgbad = sec(4ull * std::max(n_sg, sgb_tri ? n_sg_small : 0));
   // Level 0's signature side: with the batched test on, S comes from the
   // test's sums (l0_fused, tbls_launch.h; a replayed prefix of the launch
   // keeps both flags, so it takes the same path) and the bucket MSM's
@@ -882,8 +928,10 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   size_t w_mbkt = sec(msm ? sizeof(G2J) * (size_t)MSM_BUCKETS : 0);
   size_t w_mpart = sec(msm ? sizeof(G2J) * (size_t)MSM_BUCKETS * MSM_SPLIT : 0);
   size_t w_msum = sec(msm ? sizeof(G2J) * (size_t)MSM_SUM_ENTRIES : 0);
-  size_t w_sgt = sec(fused ? sizeof(G2J) * sgb_t_slices(sgb_m) * n_sg : 0);
-  size_t w_l0fsum = sec(fused ? sizeof(G2J) * (size_t)l0f_sum_entries((uint32_t)n_sg, sgb_m) : 0);
+  size_t w_sgt = sec(fused ? sizeof(G2J) * sgsec([](uint32_t m) { return (size_t)sgb_t_slices(m); }) : 0);
+  size_t w_l0fsum = sec(fused ? sizeof(G2J) * std::max<size_t>(l0f_sum_entries((uint32_t)n_sg, sgb_m),
+                                                               sgb_tri ? l0f_sum_entries((uint32_t)n_sg_small, sgb_m_small) : 0)
+                              : 0);
   size_t w_l0fu = sec(fused ? 16ull * np : 0);
   // level 0 by message: chunk sums and their member counts, Q_m, the messages' states
   const bool l0m = fused && l0m_in;
@@ -1176,6 +1224,7 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   B.sgb_ent = (uint32_t*)(dw + w_sgent);
   B.sgb_part = (G2J*)(dw + w_sgpart);
   B.sgb_rank = (uint32_t*)(dw + w_sgrank);
+  B.sgb_code = (uint32_t*)(dw + w_sgcode);
   B.sgb_bad = (uint32_t*)(dw + w_sgbad);
   B.sgb_t = (G2J*)(dw + w_sgt);
   B.l0f_sum = (G2J*)(dw + w_l0fsum);
@@ -1232,6 +1281,7 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   s->out_bytes = out_bytes;
   s->B = B;
   s->last = B;
+  s->sgb_m_small = sgb_m_small;
   s->w_out = w_out;
   s->sets = set_first != nullptr;
   s->n_sets = set_first ? n_sets : 0;
@@ -1384,6 +1434,11 @@ int tbg_replay_plan(tbg_ctx* c, const tbg_ticket* tickets, const uint32_t* n_par
       B.n_msgs = last.m0 + last.nm;
       B.l0m_n_chunks = last.ch1;  // (the prefix's own plan, see submit_impl)
       B.l0m_max_chunks = last.maxch;
+      // the subgroup test's schedule follows the prefix's own partials
+      if (B.sgb && sgb_triple(B.sgb_m)) {
+        B.sgb_m = sgb_group_size(c, B.n_partials, sl[k]->sgb_m_small, true);
+        B.sgb_split = sgb_triple(B.sgb_m) ? 1u : sgb_split_for(B.sgb_m);
+      }
     }
     bs[k] = B;
   }
@@ -1618,6 +1673,7 @@ int tbg_fetch_subgroup_schedule(tbg_ctx* c, tbg_ticket t, uint32_t* out1) {
   if (!s) return TBG_E_TICKET;
   // (the launch's own fields: the kernels took their schedule from the same ones)
   *out1 = !s->last.sgb                 ? (uint32_t)TBG_SGB_SCHED_NONE
+          : sgb_triple(s->last.sgb_m) ? (uint32_t)TBG_SGB_SCHED_TRIPLE
           : sgb_paired(s->last.sgb_m) ? (uint32_t)TBG_SGB_SCHED_PAIRED
                                       : (uint32_t)TBG_SGB_SCHED_CLASSIC;
   return TBG_OK;

@@ -184,7 +184,8 @@ struct DevBatch {
   // c_i uniform mod 13 are tested psi(Q) == [x] Q; only the members of a
   // failed group take the per-signature test (k_subgroup_sigs)
   uint32_t sgb;           // 1: the batched test runs (0: every signature is tested alone)
-  uint32_t sgb_m;         // consecutive partials per group (a power of two, SGB_M_MIN..SGB_M)
+  uint32_t sgb_m;         // consecutive partials per group (a power of two, SGB_M_MIN..SGB_M; larger: the
+                          // triple schedule, sgb_triple below)
   uint32_t sgb_split;     // slices per bucket (k_sgb_bucket / k_sgb_fold)
   uint32_t sgb_seed[8];   // secret per-batch key of the combinations' digits: always fresh OS
                           // entropy, even under a fixed rlc_seed (a predictable key would let a
@@ -192,7 +193,10 @@ struct DevBatch {
   uint32_t* sgb_off;      // [n_sg][sgb_off_stride] bucket offsets into the group's entries
   uint32_t* sgb_ent;      // [n_sg][sgb_ent_stride] entries: member << 1 | negative
   G2J* sgb_part;          // [n_sg][sgb_part_stride] bucket (slice) sums; Q_k at sgb_q_slot
-  uint32_t* sgb_rank;     // [n_sg][SGB_PBUCKETS] paired schedule: the group's buckets by decreasing entry count
+  uint32_t* sgb_rank;     // [n_sg][SGB_PBUCKETS / SGB_TBUCKETS] paired and triple schedules: the group's
+                          // buckets by decreasing entry count
+  uint32_t* sgb_code;     // [n_partials][SGB_TRIPLES] triple schedule: bucket | negative << 11 | place in
+                          // its bucket << 12 (k_sgb_tri_count -> k_sgb_tri_scatter), SGBT_NONE: no entry
   uint32_t* sgb_bad;      // [n_sg] 1: some combination is outside G2 (members tested alone)
   // fused level 0 (l0_fused below): S from the subgroup test's sums
   G2J* sgb_t;             // [n_sg][sgb_t_slices(sgb_m)] slice sums of the group's unweighted candidates
@@ -291,19 +295,53 @@ constexpr uint32_t SGB_PAIRS = SGB_K / 2;
 constexpr uint32_t SGB_PB = SGB_V + SGB_V * (2 * SGB_V + 1);  // 84: a = 0 has b = 1..6, a = 1..6 has b = -6..6
 constexpr uint32_t SGB_PBUCKETS = SGB_PAIRS * SGB_PB;         // 756 per group
 constexpr uint32_t SGB_PRANK = (SGB_PBUCKETS + 31) / 32 * 32;  // k_sgb_bucket's lane pairs per group: whole waves
-TBG_HD bool sgb_paired(uint32_t m) { return m >= SGB_PAIR_M; }
-// per-group strides of sgb_off, sgb_ent and sgb_part in either schedule
+// Triple schedule (k_sgb.hip) for groups LARGER than SGB_M: the same step
+// again, a member sorted by three digits at once, (c_3t, c_3t+1, c_3t+2) for
+// the SGB_TRIPLES triples of combinations, into one of SGB_TB = (13^3 - 1) / 2
+// buckets per triple -- 6 x 2196/2197 = 6.0 additions per member instead of
+// 8.9.  Its reductions cost ~2,400 additions per triple whatever the group's
+// size, so it pays only in groups of many thousands, which no longer fit the
+// sort's LDS: the sort runs in global memory (k_sgb_tri_*).  Only large clean
+// launches take it (sgb_plan, tbls_engine.hip; tbg_config.sgb_tri_partials,
+// sgb_tri_m); every group of at most SGB_M keeps the schedules above.
+#ifndef TBG_SGB_TRI_M
+#define TBG_SGB_TRI_M 16384
+#endif
+constexpr uint32_t SGB_TRI_M = TBG_SGB_TRI_M;    // default group size of the triple schedule
+constexpr uint32_t SGB_TRI_M_MAX = 32768;        // (entries hold member << 1 in 16 bits, codes a place < 2^20)
+constexpr uint32_t SGB_TRIPLES = SGB_K / 3;
+constexpr uint32_t SGB_TB = SGB_PB + SGB_V * (2 * SGB_V + 1) * (2 * SGB_V + 1);  // 1,098: a = 0 is a pair's 84
+constexpr uint32_t SGB_TBUCKETS = SGB_TRIPLES * SGB_TB;                          // 6,588 per group
+constexpr uint32_t SGB_TRANK = (SGB_TBUCKETS + 31) / 32 * 32;  // k_sgb_bucket's lane pairs per group: whole waves
+// k_sgb_fold's first pass per triple: the 84 sums P(a, b) over c, then the 84
+// partial sums E(v, a, sign) of the third combination (bls_sgb.h)
+constexpr uint32_t SGB_TF1 = 2 * SGB_PB;
+static_assert(SGB_TRI_M > SGB_M && SGB_TRI_M <= SGB_TRI_M_MAX && (SGB_TRI_M & (SGB_TRI_M - 1)) == 0, "SGB_TRI_M");
+TBG_HD bool sgb_triple(uint32_t m) { return m > SGB_M; }
+TBG_HD bool sgb_paired(uint32_t m) { return m >= SGB_PAIR_M && !sgb_triple(m); }
+// per-group strides of sgb_off, sgb_ent and sgb_part in each schedule
 // (paired: the SGB_PBUCKETS bucket sums, then the SGB_BUCKETS sums of
-// k_sgb_fold laid out as the classic schedule's folded buckets)
-TBG_HD uint32_t sgb_off_stride(uint32_t m) { return (sgb_paired(m) ? SGB_PBUCKETS : SGB_BUCKETS) + 1; }
-TBG_HD uint32_t sgb_ent_stride(uint32_t m) { return m * (sgb_paired(m) ? SGB_PAIRS : SGB_K); }
+// k_sgb_fold laid out as the classic schedule's folded buckets; triple: the
+// SGB_TBUCKETS bucket sums, the first pass's SGB_TRIPLES x SGB_TF1 sums, then
+// the same SGB_BUCKETS folded sums)
+TBG_HD uint32_t sgb_off_stride(uint32_t m) {
+  return (sgb_triple(m) ? SGB_TBUCKETS : sgb_paired(m) ? SGB_PBUCKETS : SGB_BUCKETS) + 1;
+}
+TBG_HD uint32_t sgb_ent_stride(uint32_t m) {
+  return m * (sgb_triple(m) ? SGB_TRIPLES : sgb_paired(m) ? SGB_PAIRS : SGB_K);
+}
+TBG_HD uint32_t sgb_rank_stride(uint32_t m) { return sgb_triple(m) ? SGB_TBUCKETS : sgb_paired(m) ? SGB_PBUCKETS : 0u; }
+constexpr uint32_t SGB_TFOLD = SGB_TBUCKETS + SGB_TRIPLES * SGB_TF1;  // the triple schedule's folded sums in a group
 TBG_HD uint32_t sgb_part_stride(uint32_t m) {
-  return sgb_paired(m) ? SGB_PBUCKETS + SGB_BUCKETS : SGB_BUCKETS * sgb_split_for(m);
+  return sgb_triple(m)   ? SGB_TFOLD + SGB_BUCKETS
+         : sgb_paired(m) ? SGB_PBUCKETS + SGB_BUCKETS
+                         : SGB_BUCKETS * sgb_split_for(m);
 }
 // Q_k of group g (k_sgb_combine's output; k_sgb_test and the fused level 0 read it)
 TBG_HD size_t sgb_q_slot(const DevBatch& B, uint32_t g, uint32_t k) {
-  return (size_t)sgb_part_stride(B.sgb_m) * g +
-         (sgb_paired(B.sgb_m) ? SGB_PBUCKETS + SGB_V * k : SGB_V * k * B.sgb_split);
+  return (size_t)sgb_part_stride(B.sgb_m) * g + (sgb_triple(B.sgb_m)   ? SGB_TFOLD + SGB_V * k
+                                                 : sgb_paired(B.sgb_m) ? SGB_PBUCKETS + SGB_V * k
+                                                                       : SGB_V * k * B.sgb_split);
 }
 // Fused level 0 (bls_rlc.h, k_msm.hip): while the batched subgroup test runs,
 // r_i is a fixed linear form of the partial's 18 subgroup digits, so S is a

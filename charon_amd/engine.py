@@ -30,9 +30,10 @@ VERIFY_RLC, VERIFY_EACH = 0, 1
 RLC_L0_AUTO, RLC_L0_ON, RLC_L0_OFF = 0, 1, 2   # tbg_config.rlc_batch
 GIDENT_OFF, GIDENT_L3, GIDENT_CHUNKS = 0, 1, 2  # tbg_config.gident
 SGB_AUTO, SGB_ON, SGB_OFF = 0, 1, 2           # tbg_config.subgroup_batch
-SGB_SCHEDULES = ("none", "classic", "paired")  # TBG_SGB_SCHED_* (tbg_fetch_subgroup_schedule)
+SGB_SCHEDULES = ("none", "classic", "paired", "triple")  # TBG_SGB_SCHED_* (tbg_fetch_subgroup_schedule)
 EXPRESS_OFF = 0xFFFFFFFF                        # tbg_config.express_partials: no express slot
 L0_DUTY_ALWAYS, L0_DUTY_NEVER = 1, 0xFFFFFFFF   # tbg_config.l0_duty_partials (0: TBG_L0_DUTY_PARTIALS)
+SGB_TRI_NEVER = 0xFFFFFFFF                      # tbg_config.sgb_tri_partials (0: TBG_SGB_TRI_PARTIALS)
 L0_MSG_ALWAYS, L0_MSG_NEVER = 1, 0xFFFFFFFF     # tbg_config.l0_msg_share (0: TBG_L0_MSG_SHARE duties per message)
 L0_NOT_RUN, L0_PASSED, L0_FAILED = 0, 1, 2     # tbg_fetch_level0
 HOST_STAT_KEYS = ["submits", "partials_submitted", "pack_ns", "enqueue_ns", "collects", "partials_collected",
@@ -107,14 +108,15 @@ class Engine:
     def __init__(self, device: int = 0, slots: int = 3, verify_mode: int = VERIFY_RLC, rlc_group: int = 0,
                  rlc_seed: int = 0, rlc_chunk: int = 0, streams_per_slot: int = 0, rlc_batch: int = 0,
                  gident: int = GIDENT_OFF, fb_window: int = 0, subgroup_batch: int = SGB_AUTO,
-                 express_partials: int = 0, l0_duty_partials: int = 0, l0_msg_share: int = 0):
+                 express_partials: int = 0, l0_duty_partials: int = 0, l0_msg_share: int = 0,
+                 sgb_tri_partials: int = 0, sgb_tri_m: int = 0):
         self._lib = _native.load()
         cfg = _native.TbgConfig(device=device, max_partials=0, max_duties=0, max_msg_bytes=0, slots=slots,
                                 verify_mode=verify_mode, rlc_group=rlc_group, rlc_seed=rlc_seed,
                                 rlc_chunk=rlc_chunk, streams_per_slot=streams_per_slot, rlc_batch=rlc_batch,
                                 gident=gident, fb_window=fb_window, subgroup_batch=subgroup_batch,
                                 express_partials=express_partials, l0_duty_partials=l0_duty_partials,
-                                l0_msg_share=l0_msg_share)
+                                l0_msg_share=l0_msg_share, sgb_tri_partials=sgb_tri_partials, sgb_tri_m=sgb_tri_m)
         h = ctypes.c_void_p()
         rc = self._lib.tbg_init(ctypes.byref(cfg), ctypes.byref(h))
         self._check(rc, "tbg_init")
@@ -318,7 +320,8 @@ class Engine:
         groups of consecutive partials tested by random combinations (0:
         every signature tested alone), how many failed, partials per group.
         With `schedule`, also the key "schedule": which schedule its kernels
-        took (tbg_fetch_subgroup_schedule: "none", "classic" or "paired")."""
+        took (tbg_fetch_subgroup_schedule: "none", "classic", "paired" or
+        "triple")."""
         out = np.zeros(3, dtype=np.uint32)
         self._check(self._lib.tbg_fetch_subgroup(self._h, ticket, _ptr(out)), "tbg_fetch_subgroup")
         res = dict(zip(["groups", "failed", "group_size"], out.tolist()))

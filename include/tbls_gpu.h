@@ -146,7 +146,18 @@ typedef struct {
                            * per duty.  Same results either way.  0 -> TBG_L0_MSG_SHARE,
                            * 1 -> every such launch with n_msgs <= n_duties,
                            * TBG_L0_MSG_NEVER -> never                                 */
+  uint32_t sgb_tri_partials; /* batched subgroup test: device batches of at least this many
+                           * partials, while the collected batches carry no measurable
+                           * non-subgroup share, sort each member by three digits at once
+                           * in groups of sgb_tri_m (6.0 G2 additions per signature
+                           * instead of 8.9; the reductions per group only pay in large
+                           * groups).  Same verdicts and bytes either way.
+                           * 0 -> TBG_SGB_TRI_PARTIALS, TBG_SGB_TRI_NEVER -> never       */
+  uint32_t sgb_tri_m;     /* its group size: a power of two, 2,048 .. 32,768
+                           * (0 -> the compiled default, 16,384)                       */
 } tbg_config;
+#define TBG_SGB_TRI_PARTIALS 262144u
+#define TBG_SGB_TRI_NEVER 0xFFFFFFFFu
 #define TBG_L0_MSG_SHARE 2u
 #define TBG_L0_MSG_NEVER 0xFFFFFFFFu
 #define TBG_L0_DUTY_PARTIALS 600000u
@@ -337,11 +348,14 @@ int tbg_fetch_subgroup(tbg_ctx* ctx, tbg_ticket ticket, uint32_t* out3);
 /* Which schedule the batched subgroup test of the batch's last run took
  * (read-only, no device work): *out1 = TBG_SGB_SCHED_NONE (every signature
  * was tested alone), TBG_SGB_SCHED_CLASSIC (one bucket per combination and
- * digit size: groups below 256 partials) or TBG_SGB_SCHED_PAIRED (buckets over
- * two combinations' digits at once: groups of 256 and more). */
+ * digit size: groups below 256 partials), TBG_SGB_SCHED_PAIRED (buckets over
+ * two combinations' digits at once: groups of 256 to 1,024) or
+ * TBG_SGB_SCHED_TRIPLE (over three at once: the large groups of clean launches
+ * of at least tbg_config.sgb_tri_partials partials). */
 #define TBG_SGB_SCHED_NONE 0
 #define TBG_SGB_SCHED_CLASSIC 1
 #define TBG_SGB_SCHED_PAIRED 2
+#define TBG_SGB_SCHED_TRIPLE 3
 int tbg_fetch_subgroup_schedule(tbg_ctx* ctx, tbg_ticket ticket, uint32_t* out1);
 /* Verification shape of a collected batch's last submit: out4 = [duties per
  * group G, duties per Miller chunk C, level 0 on (1) or off, Miller P-chunk

@@ -150,18 +150,25 @@ def main():
     duty_sum4 -= saved
     rlc_partial -= saved  # (k_rlc_partial2: the n2 inversion batched; its G1 product now from the key's table)
     hash_ -= 2 * saved
-    # batched subgroup test (k_sgb.hip, SGB_M = 1024: the paired schedule; 18
-    # combinations with digits uniform mod 13 taken two at a time, 168/169 of
-    # the digit pairs non-zero): per partial 9 * 168 / 169 mixed additions
-    # into buckets; per group and pair of combinations the 12 sums of 13
-    # bucket sums (12 additions each, the empty buckets' trivial ones counted
-    # in full), per combination the running sums over 6 of them and one
+    # batched subgroup test (k_sgb.hip) of the launch this model prices, 16
+    # batches of 10k DVs = 640,000 partials: the triple schedule in groups of
+    # SGB_TRI_M = 16384 (18 combinations with digits uniform mod 13 taken
+    # three at a time, 2196/2197 of the digit triples non-zero): per partial
+    # 6 * 2196 / 2197 mixed additions into buckets; per group and triple of
+    # combinations the first pass's 84 sums P and 72 sums E of 13 bucket sums
+    # and 12 sums E of 7 or 6, the second pass's 12 sums of 13 and 6 of 14 (one
+    # addition less than terms each, the empty buckets' trivial ones counted in
+    # full), per combination the running sums over 6 of them and one
     # psi(Q) == [x]Q test on a Jacobian Q (the affine test with its 5 mixed
-    # additions full)
+    # additions full).  (Launches below tbg_config.sgb_tri_partials run the
+    # paired schedule in groups of 1,024: 9 * 168 / 169 additions per partial
+    # and 9 * 12 * 12 fold additions per group.)
     madd, _ = measure(lib.hc_k_msm_entry, 0)  # k = 0: psi^0, one mixed addition
-    sgb_m, sgb_k = 1024, 18
-    sgb_bucket = sgb_k / 2 * 168 / 169 * madd
-    sgb_fold = sgb_k / 2 * 12 * 12 * g2_add / sgb_m  # R_a, D_v of every pair
+    sgb_m, sgb_k = 16384, 18
+    sgb_bucket = sgb_k / 3 * 2196 / 2197 * madd
+    sgb_fold1 = 84 * 12 + 6 * (12 * 12 + 6 + 5)  # P; per v: E(v, a >= 1, +-), E(v, 0, +), E(v, 0, -)
+    sgb_fold2 = 12 * 12 + 6 * 13
+    sgb_fold = sgb_k / 3 * (sgb_fold1 + sgb_fold2) * g2_add / sgb_m
     sgb_combine = sgb_k * 12 * g2_add / sgb_m  # the running sums over the 6 folded sums
     sgb_test = sgb_k * (k_subgroup + 5 * (g2_add - madd)) / sgb_m
     sgb_per_partial = sgb_bucket + sgb_fold + sgb_combine + sgb_test
@@ -283,7 +290,7 @@ def main():
             "k_decode_sigs": {"per": "partial", "mads": round(k_decode)},
             "k_subgroup_sigs": {"per": "partial", "mads": round(k_subgroup)},
             "k_sgb_bucket": {"per": "partial", "mads": round(sgb_bucket_t)},  # (with the fused level 0's sum T)
-            "k_sgb_fold": {"per": "partial", "mads": round(sgb_fold)},
+            "k_sgb_tri_fold": {"per": "partial", "mads": round(sgb_fold)},
             "k_sgb_combine": {"per": "partial", "mads": round(sgb_combine)},
             "k_sgb_test": {"per": "partial", "mads": round(sgb_test)},
             "k_hash_map": {"per": "message", "mads": round(k_hash_map)},
