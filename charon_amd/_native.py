@@ -131,6 +131,55 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 0, defines=(),
     return target
 
 
+_LLVM = "/opt/rocm/llvm/bin"
+
+
+def split_functions(asm: str):
+    """(name, body) of every function of an llvm-objdump -d listing, in file
+    order.  A function starts at "<address> <name>:" ("<name>:" under
+    --no-leading-addr)."""
+    import re
+    head = r"^(?:[0-9a-f]+ )?<([^>]+)>:\n"
+    return [(m.group(1), m.group(2)) for m in re.finditer(head + r"(.*?)(?=" + head + r"|\Z)", asm, flags=re.M | re.S)]
+
+
+def return_address_clobbers(functions, kernels):
+    """The callable functions (not kernels) that run `s_getpc_b64 s[30:31]`:
+    kernels (a .kd descriptor each) may use s[30:31] as a free pair; every
+    other function holds its return address there."""
+    import re
+    return [name for name, body in functions
+            if name not in kernels and re.search(r"s_getpc_b64\s+s\[30:31\]", body)]
+
+
+def device_functions(obj: str, disasm_flags=()):
+    """The gfx950 code of one object file, function by function: (functions,
+    kernels), `functions` a list of (name, disassembly text) in file order
+    (llvm-objdump -d with `disasm_flags`) and `kernels` the names that have a
+    .kd descriptor.
+    None for a host-only translation unit.  The .hip_fatbin section is dumped,
+    its gfx950 code object unbundled and disassembled."""
+    for tool in ("llvm-objdump", "llvm-objcopy", "clang-offload-bundler"):
+        if not os.path.exists(os.path.join(_LLVM, tool)):
+            # fail closed: the return-address guard stands between a known GPU hang and the box
+            raise RuntimeError(f"{_LLVM}/{tool} is missing: cannot read the device code of {obj}")
+    import re
+    import tempfile
+    objdump = os.path.join(_LLVM, "llvm-objdump")
+    heads = subprocess.run([objdump, "-h", obj], capture_output=True, text=True).stdout
+    if ".hip_fatbin" not in heads:
+        return None
+    with tempfile.TemporaryDirectory() as td:
+        fat, co = os.path.join(td, "fatbin"), os.path.join(td, "co")
+        subprocess.check_call([os.path.join(_LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", obj,
+                               os.path.join(td, "stripped.o")])
+        subprocess.check_call([os.path.join(_LLVM, "clang-offload-bundler"), "--unbundle", f"--input={fat}", "--type=o",
+                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"])
+        asm = subprocess.run([objdump, "-d", *disasm_flags, co], capture_output=True, text=True, check=True).stdout
+        syms = subprocess.run([objdump, "-t", co], capture_output=True, text=True, check=True).stdout
+    return split_functions(asm), set(re.findall(r"\s(\S+)\.kd\s*$", syms, flags=re.M))
+
+
 def check_return_address(obj: str) -> None:
     """Refuse a code object in which a callable function clobbers its return
     address.  When a loop body in an out-of-line device function exceeds the
@@ -139,33 +188,10 @@ def check_return_address(obj: str) -> None:
     function's return address, so the return jumps into the function again
     and the kernel never finishes (observed on gfx950).  Kernels use a free
     SGPR pair and are not affected."""
-    llvm = "/opt/rocm/llvm/bin"
-    for tool in ("llvm-objdump", "llvm-objcopy", "clang-offload-bundler"):
-        if not os.path.exists(os.path.join(llvm, tool)):
-            # fail closed: this guard stands between a known GPU hang and the box
-            raise RuntimeError(f"{llvm}/{tool} is missing: cannot run the return-address check on {obj}")
-    import re
-    import tempfile
-    heads = subprocess.run([os.path.join(llvm, "llvm-objdump"), "-h", obj], capture_output=True, text=True).stdout
-    if ".hip_fatbin" not in heads:
+    code = device_functions(obj)
+    if code is None:
         return  # host-only translation unit
-    with tempfile.TemporaryDirectory() as td:
-        fat, co = os.path.join(td, "fatbin"), os.path.join(td, "co")
-        subprocess.check_call([os.path.join(llvm, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", obj,
-                               os.path.join(td, "stripped.o")])
-        subprocess.check_call([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", f"--input={fat}", "--type=o",
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"])
-        asm = subprocess.run([os.path.join(llvm, "llvm-objdump"), "-d", co], capture_output=True, text=True,
-                             check=True).stdout
-        syms = subprocess.run([os.path.join(llvm, "llvm-objdump"), "-t", co], capture_output=True, text=True,
-                              check=True).stdout
-    # kernels (a .kd descriptor each) may use s[30:31] as a free pair; every
-    # other function holds its return address there
-    kernels = set(re.findall(r"\s(\S+)\.kd\s*$", syms, flags=re.M))
-    bad = []
-    for m in re.finditer(r"^[0-9a-f]+ <([^>]+)>:\n(.*?)(?=^[0-9a-f]+ <|\Z)", asm, flags=re.M | re.S):
-        if m.group(1) not in kernels and re.search(r"s_getpc_b64\s+s\[30:31\]", m.group(2)):
-            bad.append(m.group(1))
+    bad = return_address_clobbers(*code)
     if bad:
         raise RuntimeError(f"{obj}: long branch(es) through s[30:31] in out-of-line function(s) {bad} "
                            "(return-address clobber; would hang on the GPU) -- keep that loop body smaller")

@@ -25,31 +25,15 @@
 // keeps kernels within the instruction cache and compile times sane.
 // Out-of-line device functions.  Calls pass the large point / tower structs
 // through the scratch stack, but inlining whole call trees into the kernels
-// (-DTBG_INLINE_ALL=1) costs 15+ min of compile time, drops every kernel to
-// one wave per SIMD (AGPR spill space) and spills thousands of VGPRs in the
-// final exponentiation; and inlining only the point / quad primitives
-// (TBG_INLINE_PT=1) must not be combined with an out-of-line caller whose
-// loop body then exceeds the branch range: this compiler expands such long
-// branches through s[30:31], the caller's return address (a hang on gfx950).
-#if defined(TBG_INLINE_ALL) && TBG_INLINE_ALL
-#define TBG_NI __host__ __device__ __forceinline__
-#else
+// costs 15+ min of compile time, drops every kernel to one wave per SIMD
+// (AGPR spill space) and spills thousands of VGPRs in the final
+// exponentiation; and inlining only the point / quad primitives must not be
+// combined with an out-of-line caller whose loop body then exceeds the branch
+// range: this compiler expands such long branches through s[30:31], the
+// caller's return address (a hang on gfx950).
 #define TBG_NI __host__ __device__ __noinline__ inline
-#endif
-// Point / line / quad primitives: out of line unless TBG_INLINE_PT=1 or
-// TBG_INLINE_ALL=1 (see above).
-#ifndef TBG_INLINE_PT
-#if defined(TBG_INLINE_ALL) && TBG_INLINE_ALL
-#define TBG_INLINE_PT 1
-#else
-#define TBG_INLINE_PT 0
-#endif
-#endif
-#if TBG_INLINE_PT
-#define TBG_PT __host__ __device__ __forceinline__
-#else
+// Point / line / quad primitives: out of line too (see above).
 #define TBG_PT __host__ __device__ __noinline__ inline
-#endif
 #else
 #define TBG_HD inline
 #define TBG_NI inline

@@ -120,14 +120,7 @@ TBG_HD Fp12 quad_to_fp12(const Fp4& A0, const Fp4& A1, const Fp4& A2) {
 namespace tbg {
 
 #define TBG_DEV __device__ __forceinline__
-#ifndef TBG_INLINE_QUAD
-#define TBG_INLINE_QUAD TBG_INLINE_PT
-#endif
-#if TBG_INLINE_QUAD
-#define TBG_QUAD_FN __forceinline__
-#else
-#define TBG_QUAD_FN __noinline__
-#endif
+#define TBG_QUAD_FN __noinline__  // out of line, as the point primitives (bls_field.h TBG_PT)
 
 // Lane groups: an Fp12 lives on a TRIO of consecutive lanes of a 16-lane
 // DPP row -- 5 trios per row, lane 15 idle, so 60 of 64 lanes work; operands

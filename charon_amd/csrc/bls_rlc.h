@@ -282,15 +282,9 @@ TBG_HD Jac<F> rlc_duty_keys_l0f(uint32_t n, const Fp& c, Cand&& cand) {
 }
 
 // [r] pk from the key's resident table (PK_TAB entries, tbls_launch.h)
-#if defined(TBG_PK_W2)
 TBG_HD G1J rlc_mul_key(const G1A* tab, const uint32_t (&u)[4]) {
-#if TBG_PK_W2
   return rlc_mul_key_w2(tab, fp_from_const(G1_BETA), u);
-#else
-  return rlc_mul_table(tab[0], tab[1], fp_from_const(G1_BETA), u);
-#endif
 }
-#endif
 
 // [r] s for s in G2 (affine): pairs (s, psi(s)) and psi^2 of the same table.
 TBG_HD G2J rlc_mul_g2(const G2A& s, const uint32_t (&u)[4]) {

@@ -1,7 +1,7 @@
 // Level 1's group sums S_g = sum_i r_i s_i as one bucket MSM per group
 // (VERDICT r05 item 2), in place of a 64-bit G2 scalar multiplication per
-// partial (k_rlc_partial2: 15 doublings, 31 additions and a batched field
-// inversion each).  Reference: the per-partial CoreVerify calls of
+// partial (15 doublings, 31 additions and a batched field inversion each:
+// what k_rlc_partial2_list still does for the failed groups' candidates).  Reference: the per-partial CoreVerify calls of
 // tbls.Verify / VerifyAndAggregate (tbls/tss.go:163-197), batched per
 // k_rlc.hip's header; every verdict stays the exact per-item one.
 //
@@ -21,7 +21,7 @@
 //   k_gm_window   one lane PAIR per (group, window): T_w = sum_b (2b + 1) B_(w, b)
 //   k_gm_combine  one lane PAIR per group: S_g = sum_w 16^w T_w, affine, grp_state
 // After the group checks (k_rlc_group_final), k_gm_failed_list lists the
-// candidates of FAILED groups; k_rlc_partial2 (list mode) forms their r_i s_i
+// candidates of FAILED groups; k_rlc_partial2_list (k_pair.hip) forms their r_i s_i
 // and k_rlc_duty_sum<DSUM_FALLBACK_S> their S_d, which the chunk / duty /
 // partial levels use as before -- at 1 % invalid partials ~12 % of the groups.
 //
@@ -268,9 +268,9 @@ __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_gm_window(DevBatch B) {
   }
 }
 
-// one lane pair per group: S_g = sum_w 16^w T_w, then what k_rlc_group_lines
-// does with it: no combined duty -> GRP_EMPTY, S_g = 0 -> GRP_FAIL (its
-// chunks decide), else S_g affine for its lines (k_lines_fold<FOLD_GROUPS>)
+// one lane pair per group: S_g = sum_w 16^w T_w, then the group's state: no
+// combined duty -> GRP_EMPTY, S_g = 0 -> GRP_FAIL (its chunks decide), else
+// S_g affine for its lines (k_lines_fold<FOLD_GROUPS>), GRP_LINES
 __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_gm_combine(DevBatch B) {
   if (B.counters[CNT_L0_OK]) return;
   const uint32_t ng = gm_groups(B), G = B.rlc_group;

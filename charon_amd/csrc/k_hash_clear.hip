@@ -25,13 +25,10 @@ __device__ __forceinline__ Jac<Fp2x> px_psi(const Jac<Fp2x>& p) {
   return {f_mulc(f_conj(p.X), PSI_X), f_mulc(f_conj(p.Y), PSI_Y), f_reduce(f_conj(p.Z))};
 }
 
-// [x] p = -[|x|] p (63 doublings, 5 additions).  TBG_CLEAR_X: the additions
-// without the doubling case (bls_pair.h jac_mul_xabs_x: inputs retired early,
-// fewer live values), the rare doubling case (only points of tiny order)
-// redone with the complete formulas; 0: the complete formulas throughout.
-#ifndef TBG_CLEAR_X
-#define TBG_CLEAR_X 1
-#endif
+// [x] p = -[|x|] p (63 doublings, 5 additions): the additions without the
+// doubling case (bls_pair.h jac_mul_xabs_x: inputs retired early, fewer live
+// values), the rare doubling case (only points of tiny order) redone with the
+// complete formulas (px_mul_x_full).
 __device__ __forceinline__ Jac<Fp2x> px_mul_x_full(const Jac<Fp2x>& p) {
   Jac<Fp2x> acc = p;
 #pragma unroll 1
@@ -59,7 +56,6 @@ __device__ __noinline__ Jac<Fp2x> px_add_complete_at(const G2J* a, const G2J* b,
 // (the compiler barrier keeps the load where it is used: a base point held
 // across the 63 doublings was spilled to scratch and reloaded every step)
 __device__ __forceinline__ Jac<Fp2x> px_mul_x(const G2J& slot) {
-#if TBG_CLEAR_X
   bool exc = false;
   Jac<Fp2x> acc = px_load(slot);
 #pragma unroll 1
@@ -72,9 +68,6 @@ __device__ __forceinline__ Jac<Fp2x> px_mul_x(const G2J& slot) {
   }
   if (pair_all(!exc)) return jac_neg(acc);  // (pair-uniform)
   return px_mul_x_complete(px_load(slot));
-#else
-  return px_mul_x_full(px_load(slot));
-#endif
 }
 
 __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_hash_clear_x1(DevBatch B) {

@@ -9,8 +9,8 @@
 // The signature side is the bucket MSM of bls_msm.h: 4 mixed additions per
 // partial instead of a 64-bit G2 scalar multiplication (15 doublings, 31
 // additions and a field inversion per partial at the group levels); the key
-// side uses per-key pair tables A+- = pk +- [x]pk computed once when the key
-// table is loaded, so P_d needs no inversion per partial either.
+// side uses per-key window tables (bls_rlc.h rlc_mul_key_w2) computed once
+// when the key table is loaded, so P_d needs no inversion per partial either.
 //
 //   k_rlc_g1_l0      one lane per partial: r_i, [r_i] pk_i, bucket sizes
 //   k_msm_scan       bucket offsets (one workgroup)
@@ -33,10 +33,9 @@
 
 namespace tbg {
 
-// Table of every usable key (k_rlc_g1_l0, k_rlc_partial2): the window table
-// of bls_rlc.h (TBG_PK_W2: e0 pk + e1 [x]pk, e0 in {1, 3}, e1 in {+-1, +-3})
-// or the pair table A+ = pk + [x]pk, A- = pk - [x]pk, each entry's affine
-// conversion batched over the workgroup (bls_batchinv.h).
+// Table of every usable key (k_rlc_g1_l0, k_rlc_g1): the window table of
+// bls_rlc.h (e0 pk + e1 [x]pk, e0 in {1, 3}, e1 in {+-1, +-3}), each entry's
+// affine conversion batched over the workgroup (bls_batchinv.h).
 __global__ void __launch_bounds__(BINV_BLOCK) k_pubkey_tables(const G1A* pk, const G1A* xpk, const int32_t* status,
                                                               uint32_t n, G1A* tab) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -47,7 +46,6 @@ __global__ void __launch_bounds__(BINV_BLOCK) k_pubkey_tables(const G1A* pk, con
     p0 = pk[i];
     x0 = xpk[i];
   }
-#if TBG_PK_W2
   // e0 pk + e1 [x]pk is never the identity for a prime-order key (it would
   // need x = -e0 / e1 mod r); every thread runs every batched conversion
 #pragma unroll 1
@@ -57,20 +55,11 @@ __global__ void __launch_bounds__(BINV_BLOCK) k_pubkey_tables(const G1A* pk, con
     const bool got = block_jac_to_aff<BINV_WAVES>(e, ok, a);
     if (in) tab[(size_t)PK_TAB * i + k] = got ? a : G1A{fp_zero(), fp_zero()};
   }
-#else
-  // x0.x != p0.x for a prime-order key ([x]pk = +-pk would need x = +-1 mod r)
-  const Fp t = block_batch_inv<BINV_WAVES>(fp_reduce(fp_sub(x0.x, p0.x)), ok);  // every thread of the workgroup
-  if (!in) return;
-  G1A ap{fp_zero(), fp_zero()}, am = ap;
-  if (ok) rlc_pair_from_inv(p0, x0, t, ap, am);
-  tab[2ull * i] = ap;
-  tab[2ull * i + 1] = am;
-#endif
 }
 
 // Level-0 G1 side, one lane per partial: unusable keys are marked, every
 // candidate's r_i is drawn (no group lead: at level 0 two r = 1 partials of
-// different groups could cancel) and [r_i] pk_i computed from the key's pair
+// different groups could cancel) and [r_i] pk_i computed from the key's window
 // table; the four digits count into their buckets.
 // (Fused launches of at least l0_duty_partials partials run l0duty::k_rlc_g1_l0
 // below instead.)
@@ -268,9 +257,6 @@ __device__ __forceinline__ Jac<Fp2x> msm_bucket_scaled(const DevBatch& B, uint32
   }
   return acc;
 }
-#ifndef TBG_MSM_BUCKET_X
-#define TBG_MSM_BUCKET_X 1  // 0: the complete additions inline (139 spilled VGPRs)
-#endif
 // the doubling case of an addition (equal slice sums: crafted signatures
 // only) redone with the complete formulas, out of line
 __device__ __noinline__ Jac<Fp2x> msm_bucket_complete(const DevBatch& B, uint32_t j) {
@@ -285,25 +271,9 @@ __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_msm_bucket(DevBatch B) {
   const uint32_t j = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;
   if (j >= MSM_BUCKETS) return;
   if (B.counters[CNT_L0_BAD]) return;
-#if TBG_MSM_BUCKET_X
   bool exc = false;
   Jac<Fp2x> acc = msm_bucket_scaled<true>(B, j, exc);
   if (!pair_all(!exc)) acc = msm_bucket_complete(B, j);  // (pair-uniform)
-#else
-  Jac<Fp2x> acc = px_load(B.msm_part[MSM_SPLIT * j]);
-#pragma unroll 1
-  for (uint32_t sl = 1; sl < MSM_SPLIT; ++sl) acc = jac_add_in<Fp2x, true>(acc, px_load(B.msm_part[MSM_SPLIT * j + sl]));
-  const uint32_t m = 2 * j + 1;
-  if (m > 1 && !jac_is_inf(acc)) {
-    const Jac<Fp2x> b = acc;
-    const int top = 31 - __builtin_clz(m);
-#pragma unroll 1
-    for (int bit = top - 1; bit >= 0; --bit) {
-      acc = jac_dbl_in(acc);
-      if ((m >> bit) & 1u) acc = jac_add_in<Fp2x, true>(acc, b);
-    }
-  }
-#endif
   px_store(B.msm_bkt[j], acc);
 }
 

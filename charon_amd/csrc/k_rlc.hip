@@ -67,13 +67,15 @@ __device__ __forceinline__ uint32_t rlc_candidates(const DevBatch& B, uint32_t d
 }
 
 // ------------------------------------------------------------------ level 0
-// [r_i] s_i and [r_i] pk_i: k_rlc_g2_pair / k_rlc_g1 (k_pair.hip).
+// [r_i] pk_i: k_rlc_g1_l0 (k_msm.hip) / k_rlc_g1 (k_gmsm.hip); [r_i] s_i, for
+// the failed groups' candidates only: k_rlc_partial2_list (k_pair.hip).
 
-// One thread per duty: P_d = sum r_i pk_i (affine) and S_d = sum r_i s_i.
-// Level 0 (DSUM_L0_P) forms P_d only -- its S is the batch-wide MSM -- and a
-// duty it cannot combine (P_d = 0) makes level 0 fail; after a level-0
-// failure DSUM_FALLBACK_S adds the S_d of the duties level 0 combined (the
-// stored P-chunk products include them; S_d = 0 is just a term of the sums).
+// One thread per duty: P_d = sum r_i pk_i (affine), or S_d = sum r_i s_i.
+// Level 0 (DSUM_L0_P) and level 1 (DSUM_P) form P_d only -- their S is the
+// batch-wide sum or the group MSM's -- and a duty level 0 cannot combine
+// (P_d = 0) makes it fail; after the group checks DSUM_FALLBACK_S adds the
+// S_d of the failed groups' combined duties (the stored P-chunk products
+// include them; S_d = 0 is just a term of the sums).
 // P_d's affine conversion is batched over the workgroup (bls_batchinv.h).
 template <int PHASE>
 __global__ void __launch_bounds__(BINV_BLOCK) k_rlc_duty_sum(DevBatch B) {
@@ -84,11 +86,9 @@ __global__ void __launch_bounds__(BINV_BLOCK) k_rlc_duty_sum(DevBatch B) {
   if (phase == DSUM_P && B.counters[CNT_L0_OK]) return;
   if (phase == DSUM_FALLBACK_S) {  // (no inversion: no workgroup-wide step)
     if (!in || B.counters[CNT_L0_OK] || B.dv_state[d] != RLC_COMBINED) return;
-#if TBG_GMSM
     // after the group checks: the failed groups' duties (their r_i s_i were formed)
     const int32_t gs = B.grp_state[d / B.rlc_group];
     if (gs != GRP_FAIL && gs != GRP_GID) return;
-#endif
     G2J S = jac_inf<Fp2>();
     for (uint32_t i = B.duty_first[d]; i < B.duty_first[d + 1]; ++i)
       if (rlc_candidate(B, i)) S = jac_add(S, B.part_s[i]);
@@ -96,14 +96,12 @@ __global__ void __launch_bounds__(BINV_BLOCK) k_rlc_duty_sum(DevBatch B) {
     return;
   }
   G1J P = jac_inf<Fp>();
-  G2J S = jac_inf<Fp2>();
   int cand = 0;
   if (in) {
     for (uint32_t i = B.duty_first[d]; i < B.duty_first[d + 1]; ++i) {
       if (!rlc_candidate(B, i)) continue;
       // (G1 sums inline: the out-of-line form passes 3 x 2 Fp through scratch per addition)
       P = jac_add_in<Fp, true>(P, B.part_p[i]);
-      if (phase == DSUM_BOTH) S = jac_add(S, B.part_s[i]);
       ++cand;
     }
   }
@@ -114,45 +112,15 @@ __global__ void __launch_bounds__(BINV_BLOCK) k_rlc_duty_sum(DevBatch B) {
     B.dv_state[d] = RLC_NONE;
     return;
   }
-  if (!aff || (phase == DSUM_BOTH && jac_is_inf(S))) {
+  if (!aff) {
     B.dv_state[d] = RLC_EACH;  // degenerate combination: check the partials one by one
     if (phase == DSUM_L0_P) B.counters[CNT_L0_BAD] = 1;  // (DSUM_P: the group levels only)
     return;
   }
   B.dv_p[d] = G1A{fp_reduce(fp_neg(Pa.x)), Pa.y};  // (-x, y): the Miller steps' evaluation operands
-  if (phase == DSUM_BOTH) B.dv_s[d] = S;
   B.dv_state[d] = RLC_COMBINED;
 }
 inline dim3 duty_grid(const DevBatch& B) { return dim3((B.n_duties + BINV_BLOCK - 1) / BINV_BLOCK); }
-
-// One thread per group: S = sum of the group's S_d, affine (its Miller lines,
-// -g1 folded in: k_lines_fold.hip).
-__global__ void TBG_LAUNCH k_rlc_group_lines(DevBatch B) {
-  if (B.counters[CNT_L0_OK]) return;  // level 0 accepted the batch (k_l0_after set the groups)
-  uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t G = B.rlc_group;
-  uint32_t n_groups = (B.n_duties + G - 1) / G;
-  if (g >= n_groups) return;
-  uint32_t d0 = g * G, d1 = min(d0 + G, B.n_duties);
-  G2J S = jac_inf<Fp2>();
-  int n = 0;
-  for (uint32_t d = d0; d < d1; ++d)
-    if (B.dv_state[d] == RLC_COMBINED) {
-      S = jac_add(S, B.dv_s[d]);
-      ++n;
-    }
-  G2A Sa;
-  if (n == 0) {
-    B.grp_state[g] = GRP_EMPTY;
-    return;
-  }
-  if (!jac_to_aff(S, Sa)) {
-    B.grp_state[g] = GRP_FAIL;
-    return;
-  }
-  B.pend_pts[g] = Sa;  // lines: k_lines_fold<FOLD_GROUPS>
-  B.grp_state[g] = GRP_LINES;
-}
 
 // Fp12 values in HBM in the quad layout: trio lane q's Fp4 at 4 NL words
 // per lane (hex_load / hex_store, bls_hex.h).
@@ -890,9 +858,8 @@ static void fb_passes(const DevBatch& B, uint32_t max_entries, F&& body, bool ma
   }
 }
 
-void launch_rlc_prepare(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff, const G1A* pk_tab,
-                        const int32_t* pk_status, uint32_t n_pk, hipStream_t st,
-                        void (*after_keys)(const DevBatch&, hipStream_t)) {
+void launch_rlc_prepare(const DevBatch& B, const G1A* pk_aff, const G1A* pk_tab, const int32_t* pk_status,
+                        uint32_t n_pk, hipStream_t st, void (*after_keys)(const DevBatch&, hipStream_t)) {
   if (B.sets) launch_set_init(B, st);
   if (!B.n_duties) return;
   if (B.rlc_group == 0) {
@@ -915,16 +882,10 @@ void launch_rlc_prepare(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff
     return;
   }
   if (after_keys) after_keys(B, st);
-#if TBG_GMSM
   // the G1 products and P_d, then each group's S by its bucket MSM
   launch_rlc_g1(B, pk_tab, pk_aff, pk_status, n_pk, st);
   TBG_KLAUNCH(k_rlc_duty_sum<DSUM_P>, duty_grid(B), dim3(BINV_BLOCK), st, B);
   launch_gm_group_s(B, st);
-#else
-  launch_rlc_partials(B, pk_tab, pk_aff, pk_status, n_pk, st);
-  TBG_KLAUNCH(k_rlc_duty_sum<DSUM_BOTH>, duty_grid(B), dim3(BINV_BLOCK), st, B);
-  TBG_KLAUNCH(k_rlc_group_lines, grid_for(n_groups), dim3(kBlock), st, B);
-#endif
   launch_lines_fold(B, FOLD_GROUPS, n_groups, st);
 }
 
@@ -933,11 +894,9 @@ void launch_rlc_prepare(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff
 // goes to level 3's list).  A set launch runs none of this (k_sets.hip).
 static void launch_narrowing(const DevBatch& B, const G1A* pk_aff, uint32_t n_groups, uint32_t nch, hipStream_t st) {
   TBG_KLAUNCH(k_rlc_resolve_groups, grid_for(B.n_duties), dim3(kBlock), st, B);
-#if TBG_GMSM
   // the failed groups' r_i s_i and S_d, which every deeper level reads
   launch_gm_failed_partials(B, pk_aff, st);
   TBG_KLAUNCH(k_rlc_duty_sum<DSUM_FALLBACK_S>, duty_grid(B), dim3(BINV_BLOCK), st, B);
-#endif
   if (B.rlc_group > 1) {
     // level 1g before the chunks: its unresolved groups add to the chunk list
     uint32_t W = 1;
@@ -966,8 +925,8 @@ static void launch_narrowing(const DevBatch& B, const G1A* pk_aff, uint32_t n_gr
   }
 }
 
-void launch_rlc_check(const DevBatch& B0, const G1A* pk_aff, const G1A* xpk_aff, const G1A* pk_tab,
-                      const int32_t* pk_status, uint32_t n_pk, hipStream_t st) {
+void launch_rlc_check(const DevBatch& B0, const G1A* pk_aff, const G1A* pk_tab, const int32_t* pk_status, uint32_t n_pk,
+                      hipStream_t st) {
   if (!B0.n_duties) return;
   DevBatch B = B0;
   if (B.rlc_group != 0) {
@@ -1012,15 +971,9 @@ void launch_rlc_check(const DevBatch& B0, const G1A* pk_aff, const G1A* xpk_aff,
         launch_lines_fold(B, FOLD_GROUPS, n_groups, st);
         launch_groups_miller_hex(B, st);
       } else {
-#if TBG_GMSM
-      launch_gm_group_s(B, st);  // (G1 products, P_d and r_i: level 0's)
-#else
-      launch_rlc_partials(B, nullptr, pk_aff, pk_status, n_pk, st);  // (G1 products: level 0's)
-      TBG_KLAUNCH(k_rlc_duty_sum<DSUM_FALLBACK_S>, duty_grid(B), dim3(BINV_BLOCK), st, B);
-      TBG_KLAUNCH(k_rlc_group_lines, grid_for(n_groups), dim3(kBlock), st, B);
-#endif
-      launch_lines_fold(B, FOLD_GROUPS, n_groups, st);
-      launch_group_s_miller_hex(B, st);
+        launch_gm_group_s(B, st);  // (G1 products, P_d and r_i: level 0's)
+        launch_lines_fold(B, FOLD_GROUPS, n_groups, st);
+        launch_group_s_miller_hex(B, st);
       }
     } else {
       launch_groups_miller_hex(B, st);

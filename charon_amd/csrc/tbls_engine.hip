@@ -485,9 +485,9 @@ static int launch_chain(tbg_ctx* c, const Slot& sl, const DevBatch& B, hipEvent_
   // first on odd slots was measured no better, round 2).
   // The aggregation runs speculatively as soon as the candidates are final
   // (every candidate taken as valid), off the launch's serial tail, while
-  // level 0 is on (TBG_SPEC_ALWAYS: on every VERIFY_AGGREGATE chain, redoing
-  // only the duties with an invalid partial -- measured slower, round 5).
-  const bool spec = B.op == TBG_OP_VERIFY_AGGREGATE && (TBG_SPEC_ALWAYS || (B.rlc_batch && B.rlc_group));
+  // level 0 is on (on every VERIFY_AGGREGATE chain, redoing only the duties
+  // with an invalid partial, was measured slower, round 5).
+  const bool spec = B.op == TBG_OP_VERIFY_AGGREGATE && B.rlc_batch && B.rlc_group;
   auto msg_chain = [&]() -> int {
     HIP_TRY(hipEventRecord(ev[3], st2));
     if (verify) launch_hash_msgs(B, st2);
@@ -507,28 +507,23 @@ static int launch_chain(tbg_ctx* c, const Slot& sl, const DevBatch& B, hipEvent_
     // kernel (k_lagrange<true> 7.7 ms instead of 0.05, profiles/r04/base/
     // timeline_s20.txt).
     if (verify)
-      launch_rlc_prepare(B, pk, (const G1A*)c->d_xpk, (const G1A*)c->d_pktab, (const int32_t*)c->d_pk_status, c->n_pk,
-                         st, spec ? spec_aggregation : nullptr);
+      launch_rlc_prepare(B, pk, (const G1A*)c->d_pktab, (const int32_t*)c->d_pk_status, c->n_pk, st,
+                         spec ? spec_aggregation : nullptr);
     HIP_TRY(hipEventRecord(ev[2], st));
     return TBG_OK;
   };
-  // TBG_ALT_ORDER: on one stream, odd slots run the per-signature chain
-  // first, so launches in flight together are out of phase (one launch's
-  // latency-bound subgroup / MSM tails beside another's hash).
-  const bool alt = TBG_ALT_ORDER && st == st2 && ((&sl - c->slots.data()) & 1);
   int rc;
   if (stage < 0 || stage == 0) {
     HIP_TRY(hipEventRecord(ev[0], st));
     HIP_TRY(hipStreamWaitEvent(st2, ev[0], 0));
-    if ((rc = alt ? sig_chain() : msg_chain()) != TBG_OK) return rc;
+    if ((rc = msg_chain()) != TBG_OK) return rc;
   }
   if (stage < 0 || stage == 1)
-    if ((rc = alt ? msg_chain() : sig_chain()) != TBG_OK) return rc;
+    if ((rc = sig_chain()) != TBG_OK) return rc;
   if (stage >= 0 && stage != 2) return TBG_OK;
   HIP_TRY(hipStreamWaitEvent(st, ev[5], 0));
   HIP_TRY(hipEventRecord(ev[6], st));
-  if (verify) launch_rlc_check(B, pk, (const G1A*)c->d_xpk, (const G1A*)c->d_pktab, (const int32_t*)c->d_pk_status,
-                                 c->n_pk, st);
+  if (verify) launch_rlc_check(B, pk, (const G1A*)c->d_pktab, (const int32_t*)c->d_pk_status, c->n_pk, st);
   HIP_TRY(hipEventRecord(ev[7], st));
   if (B.op != TBG_OP_VERIFY) launch_lagrange(B, st);
   HIP_TRY(hipEventRecord(ev[8], st));
@@ -642,11 +637,11 @@ static bool l0_fits_any(uint32_t, uint32_t) { return true; }
 static void l0_shape(uint64_t nd, uint32_t n_simd, bool g_free, uint32_t& G, uint32_t& C,
                      const std::function<bool(uint32_t, uint32_t)>& fits) {
   C = 4;
-  if (!TBG_L0_SHAPE || G < 8) return;
+  if (G < 8) return;
   constexpr uint32_t L0_SHAPE_MAX_C = 10;
   uint32_t cand[3 + L0_SHAPE_MAX_C][2] = {{g_free ? 16u : G, 4}, {g_free ? 16u : G, 8}, {14, 7}};
   uint32_t n_cand = g_free ? 3u : 2u;
-  for (uint32_t c = 5; TBG_L0_SHAPE_WIDE && g_free && c <= L0_SHAPE_MAX_C; ++c) {
+  for (uint32_t c = 5; g_free && c <= L0_SHAPE_MAX_C; ++c) {
     cand[n_cand][0] = c;
     cand[n_cand][1] = c;
     ++n_cand;
@@ -882,14 +877,13 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   size_t w_bf = sec(l0 ? 4ull * 3 * 4 * NL : 0);
   size_t w_gf = sec(l0 ? 4ull * 3 * 4 * NL * grp_f_entries(ng) : 0);
   // level 1's group MSM (k_gmsm.hip): entries, offsets, bucket sums, leads, the failed groups' candidates
-  const bool gm = TBG_GMSM && G != 0;
-  size_t w_gmoff = sec(gm ? 4ull * (GM_BUCKETS + 1) * ng : 0);
-  size_t w_gment = sec(gm ? 64ull * np : 0);
-  size_t w_gmpart = sec(gm ? sizeof(G2J) * GM_BUCKETS * (size_t)ng : 0);
-  size_t w_gmlead = sec(gm ? 4ull * ng : 0);
-  size_t w_gmlist = sec(gm ? 4ull * np : 0);
-  size_t w_gmhist = sec(gm ? 4ull * 256 : 0);
-  size_t w_gmorder = sec(gm ? 4ull * GM_BUCKETS * ng : 0);
+  size_t w_gmoff = sec(G ? 4ull * (GM_BUCKETS + 1) * ng : 0);
+  size_t w_gment = sec(G ? 64ull * np : 0);
+  size_t w_gmpart = sec(G ? sizeof(G2J) * GM_BUCKETS * (size_t)ng : 0);
+  size_t w_gmlead = sec(G ? 4ull * ng : 0);
+  size_t w_gmlist = sec(G ? 4ull * np : 0);
+  size_t w_gmhist = sec(G ? 4ull * 256 : 0);
+  size_t w_gmorder = sec(G ? 4ull * GM_BUCKETS * ng : 0);
   // Batched subgroup test while the collected batches carry (almost) no
   // non-subgroup signature: groups of 1,024 partials, a failed group's members
   // tested alone (k_sgb.hip); small batches test every signature alone.
@@ -919,7 +913,7 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   // test's sums (l0_fused, tbls_launch.h; a replayed prefix of the launch
   // keeps both flags, so it takes the same path) and the bucket MSM's
   // arrays are not needed; otherwise the bucket MSM of k_msm.hip.
-  const bool fused = l0 && sgb && TBG_PK_W2;
+  const bool fused = l0 && sgb;
   const bool msm = l0 && !fused;
   size_t w_mr = sec(msm ? 8ull * np : 0);
   size_t w_moff = sec(msm ? 4ull * (MSM_BUCKETS + 1) : 0);
@@ -1184,7 +1178,7 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
     // per-partial schedule
     const double share = std::min(1.0, 10.0 * c->invalid_ema);
     const uint64_t expect = (uint64_t)((double)np * share);
-    B.fb_full = (!TBG_FB_EXPECT || G == 0 || fb_w == 0) ? 0xFFFFFFFFu
+    B.fb_full = (G == 0 || fb_w == 0) ? 0xFFFFFFFFu
                                       : (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (expect / fb_w + 1) * (uint64_t)fb_w);
   }
   B.fb_base = 0;
@@ -1455,7 +1449,6 @@ int tbg_replay_plan(tbg_ctx* c, const tbg_ticket* tickets, const uint32_t* n_par
   for (uint32_t k0 = 0; k0 < n_launches && rc == TBG_OK;) {
     uint32_t k1 = k0 + 1;
     while (k1 < n_launches && std::find(sl.begin() + k0, sl.begin() + k1, sl[k1]) == sl.begin() + k1) ++k1;
-#if TBG_REPLAY_SHAPE
     // The level-0 launches run together share the SIMDs: their shape follows
     // their duties together (l0_shape), where each launch's arena fits it.
     if (c->chunk_auto && c->rlc_auto) {
@@ -1481,23 +1474,9 @@ int tbg_replay_plan(tbg_ctx* c, const tbg_ticket* tickets, const uint32_t* n_par
           bs[k].rlc_chunk = C;
         }
     }
-#endif
-    for (int stage = 0; stage < 3 && rc == TBG_OK; ++stage) {
-#if TBG_L0_JOIN
-      // The run's level-0 Miller kernels start once every launch of the run
-      // has its signature side (S, P_d, S's lines): a Miller kernel that
-      // starts early holds the SIMDs for ~14 ms while the other launches'
-      // one-workgroup MSM tails wait for a slot behind it.
-      if (stage == 2 && k1 - k0 > 1)
-        for (uint32_t k = k0; k < k1 && rc == TBG_OK; ++k)
-          for (uint32_t j = k0; j < k1; ++j)
-            if (j != k && bs[k].rlc_batch && bs[j].rlc_batch &&
-                hipStreamWaitEvent(sl[k]->st, ev[(size_t)kChainEvents * j + 2], 0) != hipSuccess)
-              rc = TBG_E_DEVICE;
-#endif
+    for (int stage = 0; stage < 3 && rc == TBG_OK; ++stage)
       for (uint32_t k = k0; k < k1 && rc == TBG_OK; ++k)
         rc = launch_chain(c, *sl[k], bs[k], ev.data() + (size_t)kChainEvents * k, stage);
-    }
     for (uint32_t k = k0; k < k1; ++k) sl[k]->last = bs[k];
     k0 = k1;
   }
@@ -2009,8 +1988,8 @@ int tbg_fast_aggregate_verify(tbg_ctx* c, const uint32_t* pubkey_ids, const uint
   tbg::launch_decode_sigs(B, st);
   tbg::launch_hash_msgs(B, st);
   tbg::launch_h_lines(B, st);
-  tbg::launch_rlc_prepare(B, t_pk, t_xpk, nullptr, t_pkst, n, st);
-  tbg::launch_rlc_check(B, t_pk, t_xpk, nullptr, t_pkst, n, st);  // (per-item schedule: no key table)
+  tbg::launch_rlc_prepare(B, t_pk, nullptr, t_pkst, n, st);
+  tbg::launch_rlc_check(B, t_pk, nullptr, t_pkst, n, st);  // (per-item schedule: no key table)
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(status, B.partial_status, 4ull * n, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));

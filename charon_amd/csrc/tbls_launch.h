@@ -11,39 +11,13 @@
 namespace tbg {
 
 constexpr int kBlock = 64;
+// Per-key G1 tables for the RLC products [r_i] pk_i: the 8-entry window
+// table (bls_rlc.h rlc_mul_key_w2: 14 doublings + 16 additions)
+constexpr uint32_t PK_TAB = 8;  // G1A entries per key in the resident table
 // Default list positions per pass of the fallback levels' shared line buffer
 // (22.8 KB each: 0.75 GB per slot; tbg_config.fb_window overrides it).
-// Level-0 launch shape: a launch whose Miller hexads at (G, C) = (16, 4)
-// need more than one round of the device's wave slots picks (G, C) among
-// (16, 4), (16, 8), (14, 7) by rounds x hexad length (tbls_engine.hip,
-// l0_shape); 0: always (16, 4).
-// Per-key G1 tables for the RLC products [r_i] pk_i: 1 = the 8-entry window
-// table (bls_rlc.h rlc_mul_key_w2: 14 doublings + 16 additions), 0 = the
-// 2-entry pair table pk +- [x]pk (15 + 32)
-#ifndef TBG_PK_W2
-#define TBG_PK_W2 1
-#endif
-constexpr uint32_t PK_TAB = TBG_PK_W2 ? 8u : 2u;  // G1A entries per key in the resident table
-// tbg_replay_plan: the launches a plan runs together take the level-0 shape
-// of their duties together (1), or keep their submitted shapes (0)
-#ifndef TBG_REPLAY_SHAPE
-#define TBG_REPLAY_SHAPE 1
-#endif
-#ifndef TBG_L0_SHAPE
-#define TBG_L0_SHAPE 1
-#endif
-// 1 (round 6): one-chunk groups of 5 .. 10 duties are level-0 shape
-// candidates too; 0: (16, 4), (16, 8), (14, 7) only
-#ifndef TBG_L0_SHAPE_WIDE
-#define TBG_L0_SHAPE_WIDE 1
-#endif
 #ifndef TBG_FB_WINDOW
 #define TBG_FB_WINDOW 32768u
-#endif
-// 1 (round 6): the duty / partial list passes beyond the expected list
-// length launch small grids that loop (DevBatch::fb_full); 0: every pass full
-#ifndef TBG_FB_EXPECT
-#define TBG_FB_EXPECT 1
 #endif
 
 // Minimum waves per SIMD requested from the register allocator (1 lets a
@@ -349,7 +323,7 @@ TBG_HD size_t sgb_q_slot(const DevBatch& B, uint32_t g, uint32_t k) {
 // unweighted sum T of the candidates -- no bucket MSM.  The host and every
 // kernel decide the path from the launch's own fields.
 TBG_HD bool l0_fused(const DevBatch& B) {
-  return TBG_PK_W2 && B.rlc_batch && B.rlc_group && B.sgb && B.n_partials;  // (the key products use the window table)
+  return B.rlc_batch && B.rlc_group && B.sgb && B.n_partials;
 }
 // The fused level 0's key side (k_rlc_g1_l0, k_msm.hip) runs one lane per
 // DUTY -- P_d in Straus' joint form, the 18 doublings once per duty
@@ -400,14 +374,11 @@ enum MillerMode : int { MILLER_GROUPS = 0, MILLER_L0 = 1, MILLER_GROUP_S = 2 };
 //   DSUM_P: P_d only (level 1's S comes from the group MSM, k_gmsm.hip);
 //   DSUM_FALLBACK_S: S_d of the failed groups' duties, from the r_i s_i formed
 //   for them after the group checks
-enum DutySumPhase : int { DSUM_BOTH = 0, DSUM_L0_P = 1, DSUM_FALLBACK_S = 2, DSUM_P = 3 };
+enum DutySumPhase : int { DSUM_L0_P = 1, DSUM_FALLBACK_S = 2, DSUM_P = 3 };
 // Level 1's group MSM (k_gmsm.hip): each 16-bit digit a_k of r_i (bls_rlc.h)
 // read as four 4-bit windows of signed binary digits, v = 2 nibble - 15 (odd,
 // |v| <= 15): 16 entries per partial into GM_BUCKETS = 4 windows x 8 buckets
 // (|v| = 2b + 1) per group.
-#ifndef TBG_GMSM
-#define TBG_GMSM 1  // 0: the per-partial products r_i s_i for every candidate (k_rlc_partial2, before round 6)
-#endif
 constexpr uint32_t GM_W = 4, GM_V = 8, GM_BUCKETS = GM_W * GM_V;
 
 // Flags in the fallback lists (k_rlc.hip): the entry's sum is the point at
@@ -432,21 +403,6 @@ TBG_HD void fb_pass_loop(const DevBatch& B, uint32_t first, uint32_t stride, uin
   }
 }
 
-// 1: every VERIFY_AGGREGATE chain aggregates speculatively and redoes only
-// the duties with an invalid partial; 0 (default): speculate only while level
-// 0 runs, aggregate every duty again after a failed level 0.  Measured at 1 %
-// invalid (level 0 off) and on config 5 (round 5, profiles/r05/inv1/): 1.48 /
-// 1.47 M vs 1.49 / 1.50 M and 1.17 / 1.19 M vs 1.24 / 1.24 M -- the
-// speculative pass's throughput cost outweighs the shorter redo at the tail.
-#ifndef TBG_SPEC_ALWAYS
-#define TBG_SPEC_ALWAYS 0
-#endif
-#ifndef TBG_ALT_ORDER
-#define TBG_ALT_ORDER 0
-#endif
-#ifndef TBG_L0_JOIN
-#define TBG_L0_JOIN 0
-#endif
 // Participation of a partial in its duty's aggregate.  SPEC: the
 // speculative aggregation that runs BEFORE verification while level 0 is on
 // (launch_chain): every candidate counts as valid, which is what a level-0
@@ -500,12 +456,11 @@ void launch_h_lines(const DevBatch& B, hipStream_t st);
 // after_keys (optional) is enqueued once the candidates are final (the
 // ERR_PUBKEY marks made), before the level-0 bucket MSM: the chain's
 // speculative aggregation goes there, off the Miller kernel's critical path
-void launch_rlc_prepare(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff, const G1A* pk_tab,
-                        const int32_t* pk_status, uint32_t n_pk, hipStream_t st,
-                        void (*after_keys)(const DevBatch&, hipStream_t) = nullptr);
+void launch_rlc_prepare(const DevBatch& B, const G1A* pk_aff, const G1A* pk_tab, const int32_t* pk_status,
+                        uint32_t n_pk, hipStream_t st, void (*after_keys)(const DevBatch&, hipStream_t) = nullptr);
 // pk_tab: for the group levels' G1 products after a void or failed fused level 0
-void launch_rlc_check(const DevBatch& B, const G1A* pk_aff, const G1A* xpk_aff, const G1A* pk_tab,
-                      const int32_t* pk_status, uint32_t n_pk, hipStream_t st);
+void launch_rlc_check(const DevBatch& B, const G1A* pk_aff, const G1A* pk_tab, const int32_t* pk_status, uint32_t n_pk,
+                      hipStream_t st);
 void launch_lines_fold(const DevBatch& B, int kind, uint32_t max_entries, hipStream_t st);
 // set launches (k_sets.hip): set_status to VALID before the checks; after
 // level 1, k_set_resolve in place of k_rlc_resolve_groups; after level 3, the
@@ -533,13 +488,10 @@ inline uint32_t l0m_groups(const DevBatch& B) { return (B.n_msgs + B.rlc_group -
 void launch_groups_miller_hex(const DevBatch& B, hipStream_t st);
 // after a level-0 failure: the groups' S Miller products only (k_miller_hex.hip)
 void launch_group_s_miller_hex(const DevBatch& B, hipStream_t st);
-// pk_tab: the keys' pair tables (k_pubkey_tables); unused after a level-0 failure (level 0 formed the G1 products)
-void launch_rlc_partials(const DevBatch& B, const G1A* pk_tab, const G1A* pk_aff, const int32_t* pk_status,
-                         uint32_t n_pk, hipStream_t st);
 // level 1 by group MSMs (k_gmsm.hip): the G1 products and key marks (no
-// level 0), the groups' S in affine form in pend_pts (grp_state set as
-// k_rlc_group_lines does), and after the group checks the failed groups'
-// r_i s_i (k_pair.hip, list mode) and S_d
+// level 0), the groups' S in affine form in pend_pts (grp_state GRP_LINES, or
+// GRP_FAIL for a degenerate sum), and after the group checks the failed
+// groups' r_i s_i (k_pair.hip, list mode) and S_d
 void launch_rlc_g1(const DevBatch& B, const G1A* pk_tab, const G1A* pk_aff, const int32_t* pk_status, uint32_t n_pk,
                    hipStream_t st);
 void launch_gm_group_s(const DevBatch& B, hipStream_t st);
@@ -547,7 +499,7 @@ void launch_gm_failed_partials(const DevBatch& B, const G1A* pk_aff, hipStream_t
 void launch_rlc_partials_list(const DevBatch& B, const G1A* pk_aff, hipStream_t st);
 // spec: the speculative pass (level 0 on, before verification; skipped when
 // level 0 already cannot pass); the regular pass then returns at once if
-// level 0 passed (TBG_SPEC_ALWAYS: see above)
+// level 0 passed
 void launch_lagrange(const DevBatch& B, hipStream_t st, bool spec = false);
 void launch_aggregate(const DevBatch& B, hipStream_t st, bool spec = false);
 void launch_aggregate_finish(const DevBatch& B, hipStream_t st, bool spec = false);

@@ -574,7 +574,7 @@ void hc_stage_duty_sum(int n) {
   G1A a;
   jac_to_aff(accP, a);
 }
-// k_rlc_group_lines for G duties
+// a group's S as the sum of G duties' S_d (the work model's group-sum stage)
 void hc_stage_group_lines(int G) {
   G2J S = jac_from_aff(g_sig), S1 = jac_dbl(S);
 #if defined(TBG_COUNT_OPS)

@@ -148,7 +148,7 @@ def main():
     agg -= saved
     duty_sum_p4 -= saved
     duty_sum4 -= saved
-    rlc_partial -= saved  # (k_rlc_partial2: the n2 inversion batched; its G1 product now from the key's table)
+    rlc_partial -= saved  # (k_rlc_partial2_list: the n2 inversion batched; the G1 product from the key's table)
     hash_ -= 2 * saved
     # batched subgroup test (k_sgb.hip) of the launch this model prices, 16
     # batches of 10k DVs = 640,000 partials: the triple schedule in groups of

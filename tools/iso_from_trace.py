@@ -9,7 +9,7 @@ import csv
 import json
 import sys
 
-CHAIN = ["k_decode_sigs", "k_rlc_partial", "k_rlc_duty_sum", "k_rlc_group_lines", "k_hash_msgs", "k_lines_h",
+CHAIN = ["k_decode_sigs", "k_rlc_partial", "k_rlc_duty_sum", "k_gm_combine", "k_hash_msgs", "k_lines_h",
          "k_rlc_miller_chunks", "k_rlc_group_final"]
 
 
