@@ -339,8 +339,10 @@ TBG_HD int32_t g2_decompress_t(const uint8_t* b, G2A& out, Keep keep = Keep{}) {
   const Fp2 rhs = fp2_reduce(fp2_add(fp2_mul(fp2_sqr(x), x), fp2_from_const(B2_M)));
   Fp2 y;
   if (!(INL ? fp2_sqrt_in<TBG_DECODE_WIN>(rhs, y, keep) : fp2_sqrt(rhs, y))) return DEC_ERR_NOT_ON_CURVE;
-  if ((uint32_t)fp2_lex_largest(y) != s_flag) y = fp2_reduce(fp2_neg(y));
-  out.y = y;
+  // reduced in both cases: the root's non-residue arm leaves c1 = 16p - x0, and
+  // the stored point is read by every later stage as a reduced element (< 2p)
+  if ((uint32_t)fp2_lex_largest(y) != s_flag) y = fp2_neg(y);
+  out.y = fp2_reduce(y);
   if (SUBGROUP && !(INL ? g2_in_subgroup_aff_in(out) : g2_in_subgroup(jac_from_aff(out)))) return DEC_ERR_SUBGROUP;
   return DEC_OK;
 }

@@ -1,5 +1,5 @@
 """Device (gfx950) unit harness for the lane-cooperative field arithmetic, the
-lane-pair G2 group law and the hash-to-G2 kernel chain.
+lane-pair G2 group law, the hash-to-G2 kernel chain and the decode kernels.
 
 TEST TOOLING ONLY -- see devcheck.hip.  The GPU twin of tests/hostcheck:
 thin kernels around the product headers' device functions, built with the
@@ -10,8 +10,10 @@ cofactor clearing's out-of-line rare cases).  Never loaded by charon_amd.
 devcheck_h2c.hip and devcheck_h2c_clear.hip #include the product's
 k_hash.hip and k_hash_clear.hip themselves, each with the per-unit flags
 charon_amd/_native.py gives that unit, so dc_h2c runs the product's own hash
-kernels stage by stage on injected inputs.  The library therefore defines
-tbg::launch_hash_msgs and the kernels' host stubs under the product's names:
+kernels stage by stage on injected inputs; devcheck_decode.hip does the same
+with k_decode.hip for dc_decode_sigs / dc_decode_pubkeys.  The library
+therefore defines tbg::launch_hash_msgs, tbg::launch_decode_sigs and the
+kernels' host stubs under the product's names:
 it is linked with devcheck.map (only dc_* exported, everything else local)
 and -Bsymbolic, and build() refuses a library that exports a tbg:: symbol, so
 libdevcheck.so and libtbls_gpu.so each call their own code when both are
@@ -29,9 +31,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # devcheck_h2c.hip / devcheck_h2c_clear.hip: the hash-to-G2 chain, one source
 # per product unit they include (INCLUDES: the flags of _native.UNIT_FLAGS
 # follow the included unit)
+# devcheck_decode.hip: the decode kernels, k_decode.hip included the same way
 SRCS = [os.path.join(HERE, f) for f in ("devcheck.hip", "devcheck_g2.hip", "devcheck_h2c.hip",
-                                        "devcheck_h2c_clear.hip")]
-INCLUDES = {"devcheck_h2c.hip": "k_hash.hip", "devcheck_h2c_clear.hip": "k_hash_clear.hip"}
+                                        "devcheck_h2c_clear.hip", "devcheck_decode.hip")]
+INCLUDES = {"devcheck_h2c.hip": "k_hash.hip", "devcheck_h2c_clear.hip": "k_hash_clear.hip",
+            "devcheck_decode.hip": "k_decode.hip"}
 LIB = os.path.join(HERE, "libdevcheck.so")
 MAP = os.path.join(HERE, "devcheck.map")
 CSRC = os.path.join(os.path.dirname(os.path.dirname(HERE)), "charon_amd", "csrc")
@@ -129,11 +133,17 @@ SIGNATURES = {
     "dc_h2c_binv_block": [],
     "dc_h2c": [_I, _I, _U, ctypes.c_char_p, _U32P, _U32P, _U32P, _U32P, _I32P, _U],
     "dc_h2c_sqrt": [_U32P, _U32P, _U32P, _U, _U],
+    "dc_decode_sticky_error": [],
+    "dc_decode_binv_block": [],
+    "dc_decode_cnt_words": [],
+    "dc_decode_msm_buckets": [],
+    "dc_decode_sigs": [_I, _I, _U, ctypes.c_char_p, _U32P, _I32P, _U32P, _U32P, _U, _U, _U, _U32P, _U],
+    "dc_decode_pubkeys": [_U, ctypes.c_char_p, _U32P, _U32P, _I32P, _U],
 }
 
 # operation codes (devcheck.hip's enums)
 FP_OPS = ["mul", "mul2", "sqr", "add", "sub", "addl_mul", "subl_mul", "neg", "negl_mul", "mul_small", "reduce",
-          "canon", "inv", "inv_fermat", "from_signed"]
+          "canon", "inv", "inv_fermat", "from_signed", "lex"]
 ROW_OPS = ["mul", "mul2", "reduce", "norm"]
 R12_OPS = ["mul", "cyc", "frob", "conj", "fe", "isone"]
 HEX_OPS = ["mul", "sqr", "cyc", "frob", "conj", "line", "inv", "fe", "isone"]
@@ -143,6 +153,8 @@ G2_OPS = ["add_x", "add_aff_x", "dbl_lo", "add_in", "add_aff_in", "psi", "mul_xa
           "in_subgroup_aff", "clear_cofactor", "sgb_sums", "sgb_sums_complete", "sgb_fold", "sgb_fold_complete"]
 # devcheck_h2c.hip: dc_h2c's stages (MAP_MSG and MAP_U are the two forms of the first one)
 H2C_STAGES = ["MAP_MSG", "MAP_U", "SSWU", "CLEAR_X1", "CLEAR_X2", "CLEAR_FIN", "AFFINE"]
+# devcheck_decode.hip: dc_decode_sigs' stages (k_decode_sigs, k_subgroup_sigs)
+DECODE_STAGES = ["DECODE", "SUBGROUP"]
 
 
 def lib():

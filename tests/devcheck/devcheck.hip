@@ -80,7 +80,7 @@ __device__ __forceinline__ void st_fp(uint32_t* p, const Fp& a) {
 // lane-private Fp (bls_field.h): one operand tuple per thread
 enum {
   FP_MUL, FP_MUL2, FP_SQR, FP_ADD, FP_SUB, FP_ADDL_MUL, FP_SUBL_MUL, FP_NEG, FP_NEGL_MUL, FP_MUL_SMALL, FP_REDUCE,
-  FP_CANON, FP_INV, FP_INV_FERMAT, FP_FROM_SIGNED, FP_NOPS
+  FP_CANON, FP_INV, FP_INV_FERMAT, FP_FROM_SIGNED, FP_LEX, FP_NOPS
 };
 template <int OP>
 __global__ void __launch_bounds__(64) k_fp(const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d,
@@ -103,7 +103,11 @@ __global__ void __launch_bounds__(64) k_fp(const uint32_t* a, const uint32_t* b,
   else if constexpr (OP == FP_CANON) r = fp_canon(ld_fp(a + o));
   else if constexpr (OP == FP_INV) r = fp_inv(ld_fp(a + o));
   else if constexpr (OP == FP_INV_FERMAT) r = fp_inv_fermat(ld_fp(a + o));
-  else r = fp_from_signed((const int32_t*)a + o);
+  else if constexpr (OP == FP_FROM_SIGNED) r = fp_from_signed((const int32_t*)a + o);
+  else {  // the sign rule's comparison: the verdict in word 0, the other words 0
+    r = fp_zero();
+    r.l[0] = fp_lex_largest_canon(fp_from_mont(ld_fp(a + o))) ? 1u : 0u;
+  }
   st_fp(out + o, r);
 }
 
@@ -284,7 +288,7 @@ int dc_binv_waves(void) { return BINV_WAVES; }
 // lane-private Fp: n tuples, operands a..d (null where the op takes none), 14 words each
 int dc_fp(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t k,
           uint32_t* out, uint32_t n) {
-  static const int need[FP_NOPS] = {2, 4, 1, 2, 2, 3, 3, 1, 2, 1, 1, 1, 1, 1, 1};
+  static const int need[FP_NOPS] = {2, 4, 1, 2, 2, 3, 3, 1, 2, 1, 1, 1, 1, 1, 1, 1};
   if (op < 0 || op >= FP_NOPS || n == 0 || !out) return -1;
   const uint32_t* given[4] = {a, b, c, d};
   for (int i = 0; i < need[op]; ++i)
@@ -310,6 +314,7 @@ int dc_fp(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const
     DC_CASE(k_fp, FP_INV, da, db, dc, dd, k, dout, n)
     DC_CASE(k_fp, FP_INV_FERMAT, da, db, dc, dd, k, dout, n)
     DC_CASE(k_fp, FP_FROM_SIGNED, da, db, dc, dd, k, dout, n)
+    DC_CASE(k_fp, FP_LEX, da, db, dc, dd, k, dout, n)
   }
   return R.finish();
 }

@@ -222,7 +222,14 @@ def fp_cases():
     fs += [row for row in row_values() if abs(val(row)) < 8 * P][:40]
     fs += [signed_limbs(rng.randrange(-8 * P + 1, 8 * P)) for _ in range(20)]
     c["from_signed"] = [(a,) for a in fs]
+    # the sign rule's comparison c > (p - 1) / 2 on and beside its boundary (no decodable point puts a y
+    # there): Montgomery forms of the canonical value, canonical limbs and the same plus p
+    lex = LEX_EDGES + [(P - 3) // 2, (P + 3) // 2, 2, P - 2] + [rng.randrange(P) for _ in range(8)]
+    c["lex"] = [(mont(v),) for v in lex] + [(limbs(v * R % P + P),) for v in lex]
     return c
+
+
+LEX_EDGES = [0, 1, (P - 1) // 2, (P + 1) // 2, P - 1]
 
 
 def limbs_sub16p():
@@ -268,6 +275,8 @@ def fp_expect(op, t):
         return ("mod", pow(v[0], P - 2, P) * R * R, 2 * P)
     if op == "from_signed":
         return ("mod", v[0], 2 * P)
+    if op == "lex":  # fp_lex_largest_canon(fp_from_mont(a)): 1 or 0 in word 0
+        return ("exact", int(v[0] * RINV % P > (P - 1) // 2))
     raise KeyError(op)
 
 

@@ -153,7 +153,8 @@ def jac(a, lam=(1, 0)):
 def _fp_words(v, form):
     """A coordinate's component as raw limbs: canonical Montgomery form, the
     same plus p (the top of [0, 2p), the range f_reduce leaves), or
-    16p - (-v): a negated value before its reduction (decoded y coordinates)."""
+    16p - (-v): a negated value before its reduction (what the square root's
+    non-residue arm leaves in y.c1; the decoder reduces it before it stores)."""
     m = v * eo.R % P
     if form == "plus_p":
         return eo.limbs(m + P)

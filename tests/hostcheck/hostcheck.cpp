@@ -1236,7 +1236,8 @@ static Fp raw_in(const uint32_t* l) {
   return r;
 }
 // op: mul, mul2, sqr, add, sub, addl_mul, subl_mul, neg, negl_mul, mul_small,
-// reduce, canon, inv, inv_fermat, from_signed (0..14); -1 for an unknown op
+// reduce, canon, inv, inv_fermat, from_signed, lex (0..15); -1 for an unknown
+// op.  lex: fp_lex_largest_canon(fp_from_mont(a)) in word 0, the other words 0
 int hc_fp_op_raw(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t k,
                  uint32_t* out) {
   Fp r;
@@ -1256,6 +1257,7 @@ int hc_fp_op_raw(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c
     case 12: r = fp_inv(raw_in(a)); break;
     case 13: r = fp_inv_fermat(raw_in(a)); break;
     case 14: r = fp_from_signed((const int32_t*)a); break;
+    case 15: r = fp_zero(); r.l[0] = fp_lex_largest_canon(fp_from_mont(raw_in(a))) ? 1u : 0u; break;
     default: return -1;
   }
   for (int i = 0; i < NL; ++i) out[i] = r.l[i];
@@ -1345,5 +1347,45 @@ int hc_sqrt_or_z(const uint32_t* a, uint32_t* root) {
   const bool done = fp2_sqrt_or_z_in<SSWU_WIN>(raw_fp2(a), r, sq);
   raw_out(root, r);
   return (done ? 1 : 0) | (sq ? 2 : 0);
+}
+// The host twins of tests/devcheck's decode entries (tests/edge_decode.py).
+// k_decode_sigs' body on 96 bytes: the DecodeStatus and, as the kernel stores
+// them, the raw limbs of x and y (zero after a failure), so a limb form
+// outside [0, 2p) shows ...
+int hc_g2_decode_raw(const uint8_t* sig96, uint32_t* aff56) {
+  G2A a{fp2_zero(), fp2_zero()};
+  const int st = g2_decompress_t<true, false>(sig96, a);
+  if (st != DEC_OK) a = G2A{fp2_zero(), fp2_zero()};
+  raw_out(aff56, a.x);
+  raw_out(aff56 + 2 * NL, a.y);
+  return st;
+}
+// ... and k_subgroup_sigs' body on a stored point (56 raw words, any limb
+// form the decoder may leave): bit 0 the verdict, bit 1 `exc`
+int hc_subgroup_raw(const uint32_t* aff56) {
+  const G2A a{raw_fp2(aff56), raw_fp2(aff56 + 2 * NL)};
+  const Aff<Fp2p> p{pp_from(a.x), pp_from(a.y)};
+  bool exc = false;
+  bool ok = g2_in_subgroup_aff_g(p, exc);
+  if (exc) ok = g2_in_subgroup(jac_from_aff(a));
+  return (ok ? 1 : 0) | (exc ? 2 : 0);
+}
+// k_decode_pubkeys' per-key work on 48 bytes: the status, the key and [x] key
+// as raw limbs (28 words each; zero after a failure)
+int hc_g1_decode_raw(const uint8_t* pk48, uint32_t* out28, uint32_t* outx28) {
+  G1A a{fp_zero(), fp_zero()}, ax = a;
+  int st = g1_decompress(pk48, a);
+  bool ok = false;
+  if (st == DEC_OK) ok = jac_to_aff(jac_neg(jac_mul_xabs(jac_from_aff(a))), ax);
+  if (st != DEC_OK || !ok) {
+    if (st == DEC_OK) st = DEC_IDENTITY;
+    a = G1A{fp_zero(), fp_zero()};
+    ax = a;
+  }
+  for (int i = 0; i < NL; ++i) {
+    out28[i] = a.x.l[i]; out28[NL + i] = a.y.l[i];
+    outx28[i] = ax.x.l[i]; outx28[NL + i] = ax.y.l[i];
+  }
+  return st;
 }
 }

@@ -248,8 +248,8 @@ def test_checker_sees_a_wrong_word():
 
 
 def test_both_libraries_run_their_own_kernels_in_one_process():
-    """libdevcheck.so holds a second copy of the hash kernels and of
-    launch_hash_msgs under the product's names: with the engine library
+    """libdevcheck.so holds a second copy of the hash and decode kernels and
+    of launch_hash_msgs / launch_decode_sigs under the product's names: with the engine library
     loaded and used before and after, each still runs its own code."""
     import __graft_entry__ as entry
     if _STATE["rc"]:
@@ -258,4 +258,12 @@ def test_both_libraries_run_their_own_kernels_in_one_process():
     msgs = eh.messages()[:2]
     before, after, haff, hst = run("MAP_MSG", "AFFINE", 2, msgs=msgs)
     check_affine_out("both", haff, hst, 2, [eh.hash_point(m) for m in msgs])
+    # ... and of the decode kernels and their launchers (devcheck_decode.hip)
+    from tests import edge_decode as ed
+    from tests.test_gpu_devcheck_decode import check_keys, check_sigs, run_keys, run_sigs
+    keys = ed.g1_entries()[:3]
+    check_keys("both", *run_keys(keys), keys)
+    sigs = ed.g2_entries()[:5]
+    aff, st, _, _ = run_sigs("DECODE", "SUBGROUP", len(sigs), sigs=[e.data for e in sigs])
+    check_sigs("both", aff, st, sigs, True)
     entry.smoke()
