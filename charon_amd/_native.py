@@ -239,6 +239,7 @@ class TbgConfig(ctypes.Structure):
         ("l0_msg_share", ctypes.c_uint32),
         ("sgb_tri_partials", ctypes.c_uint32),
         ("sgb_tri_m", ctypes.c_uint32),
+        ("l0_tail_partials", ctypes.c_uint32),
     ]
 
 

@@ -20,8 +20,9 @@
 //   k_msm_tree, k_msm_tree_final  the sum of the scaled buckets (LDS trees), S affine
 // While the batched subgroup test runs for the launch (l0_fused, tbls_launch.h)
 // the k_msm_* kernels do not run: r_i is a form of the partial's subgroup
-// digits (bls_rlc.h, top) and S comes from that test's sums -- see "fused
-// level 0" below (k_l0f_reduce, k_l0f_fold, k_l0f_horner).
+// digits (bls_rlc.h, top) and S comes from that test's sums, formed by the
+// first workgroups of k_rlc_g1_l0's own grid -- see "the S role" below -- or, in
+// launches too small to hide it there, by k_l0f_reduce, k_l0f_fold, k_l0f_horner.
 #define TBG_ADD_DBL_INLINE 1
 #ifndef TBG_SCHED_FENCE
 #define TBG_SCHED_FENCE 1  // products in program order: fits the pair kernels in 256 VGPRs (bls_field.h)
@@ -30,8 +31,116 @@
 #include "bls_msm.h"
 #include "bls_pair.h"
 #include "bls_batchinv.h"
+#include "bls_l0tail.h"
 
 namespace tbg {
+
+// ------------------------------------------------------------ the S role
+// Fused level 0's signature side (bls_l0tail.h): S from the batched subgroup
+// test's sums -- the 18 columns Qbar_k = sum over the groups of Q_k
+// (k_sgb_combine left Q_k in the first slot of combination k's buckets,
+// k_sgb_test proved it in G2) and the column T (k_sgb_bucket's slice sums).
+// In a fused launch of at least l0_tail_partials partials (l0_tail,
+// tbls_launch.h) the key-side grid below starts with l0f_s_blocks()
+// workgroups that run l0f_s_role and return; every other workgroup runs the
+// key side on blockIdx.x - n_s.  The role reads nothing the key side writes
+// and writes only l0f_sum, its counters, batch_pt and (S = 0) CNT_L0_BAD.
+// A failed subgroup group voids level 0 (its Q_k are not in G2 and its
+// members are about to be tested alone: k_sgb.hip sets the flag with
+// sgb_bad), as does a key mark and S = 0; the role runs all the same.
+//
+// Hand-off between workgroups, which run on different XCDs with private L2s:
+// plain stores, the wave's s_waitcnt vmcnt(0), lane 0's agent-scope release
+// fence, s_waitcnt vmcnt(0) again, then a relaxed agent-scope fetch_add; the
+// last arriver runs an agent-scope acquire fence, s_waitcnt vmcnt(0) and the
+// workgroup barrier before it loads another workgroup's sums.
+static_assert(L0T_QCOLS == SGB_K && L0T_COLS == L0F_COLS && L0T_PAIRS == L0F_PAIRS && L0T_PER == L0F_PER,
+              "bls_l0tail.h: the chunking of tbls_launch.h");
+struct L0tDev {
+  using F = Fp2x;
+  using V = Jac<Fp2x>;
+  const G2J* sgb_part;
+  const G2J* sgb_t;
+  G2J* sum;
+  uint32_t* counters;
+  G2A* batch_pt;
+  uint32_t sgb_m, sgb_split;
+  Jac<Fp2x>* lds;  // [kBlock]
+
+  template <class Fn>
+  TBG_DEV V per_pair(uint32_t n, Fn&& f) const {
+    const uint32_t pr = threadIdx.x >> 1;
+    V acc = jac_inf<Fp2x>();
+    if (pr < n) acc = f(pr);
+    return acc;
+  }
+  // (every lane of the wave calls it; the barrier is the one wave's own)
+  TBG_DEV V tree(V acc, uint32_t n) const {
+    const uint32_t t = threadIdx.x, pr = t >> 1;
+#pragma unroll 1
+    for (uint32_t s = 1; s < n; s <<= 1) {
+      lds[t] = acc;
+      __syncthreads();
+      if ((pr & (2 * s - 1)) == 0 && pr + s < n) {
+        const V o = lds[t + 2 * s];
+        acc = jac_add(acc, o);
+      }
+      __syncthreads();
+    }
+    return acc;
+  }
+  TBG_DEV V load_q(uint32_t g, uint32_t col) const { return px_load(sgb_part[sgb_q_slot(sgb_m, sgb_split, g, col)]); }
+  TBG_DEV V load_t(uint32_t a) const { return px_load(sgb_t[a]); }
+  TBG_DEV V load_sum(uint32_t i) const { return px_load(sum[i]); }
+  TBG_DEV void store_sum(uint32_t i, const V& p) const {
+    if ((threadIdx.x >> 1) == 0) px_store(sum[i], p);
+  }
+  TBG_DEV uint32_t arrive(uint32_t* counter) const {
+    __asm__ __volatile__("s_waitcnt vmcnt(0)" ::: "memory");  // the storing wave (there is one)
+    uint32_t ticket = 0;
+    if (threadIdx.x == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      __asm__ __volatile__("s_waitcnt vmcnt(0)" ::: "memory");  // (the compiler may drop the fence's own wait)
+      ticket = __hip_atomic_fetch_add((__attribute__((address_space(1))) uint32_t*)counter, 1u, __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_AGENT);  // (a global access, not a flat one)
+    }
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)ticket);
+  }
+  TBG_DEV uint32_t arrive_col(uint32_t col) const { return arrive(counters + CNT_L0F_COL + col); }
+  TBG_DEV uint32_t arrive_done() const { return arrive(counters + CNT_L0F_DONE); }
+  TBG_DEV void acquire() const {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    __asm__ __volatile__("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+  TBG_DEV void finish(const V& S) const {
+    if ((threadIdx.x >> 1) != 0) return;
+    if (jac_is_inf(S)) {
+      if (pair_par() == 0) counters[CNT_L0_BAD] = 1;  // S = 0: no lines; the group levels decide
+      return;
+    }
+    const Fp2x zi = f_inv(S.Z);
+    const Fp2x zi2 = f_sqr(zi);
+    px_store(*batch_pt, Aff<Fp2x>{f_mul(S.X, zi2), f_mul(S.Y, f_mul(zi2, zi))});
+  }
+};
+
+// Out of line: its registers and spills stay its own, the key role's code is
+// what it was.  (Block-uniform: a whole workgroup is in the role or not.)
+__device__ __noinline__ void l0f_s_role(const G2J* sgb_part, const G2J* sgb_t, G2J* sum, uint32_t* counters,
+                                        G2A* batch_pt, uint32_t sgb_m, uint32_t sgb_split, uint32_t n_sg) {
+  __shared__ Jac<Fp2x> lds[kBlock];
+  L0tDev env{sgb_part, sgb_t, sum, counters, batch_pt, sgb_m, sgb_split, lds};
+  l0t_block(env, l0t_shape(n_sg, sgb_t_slices(sgb_m)), blockIdx.x);
+}
+// true: this workgroup was one of the launch's n_s S-role workgroups and is done
+TBG_DEV bool l0f_s_block(const DevBatch& B, uint32_t n_s) {
+  if (blockIdx.x >= n_s) return false;
+  TBG_URGENT();  // a few waves with a long chain beside thousands of key waves
+  l0f_s_role(B.sgb_part, B.sgb_t, B.l0f_sum, B.counters, B.batch_pt, B.sgb_m, B.sgb_split,
+             sgb_groups(B.n_partials, B.sgb_m));
+  return true;
+}
 
 // Table of every usable key (k_rlc_g1_l0, k_rlc_g1): the window table of
 // bls_rlc.h (e0 pk + e1 [x]pk, e0 in {1, 3}, e1 in {+-1, +-3}), each entry's
@@ -62,9 +171,12 @@ __global__ void __launch_bounds__(BINV_BLOCK) k_pubkey_tables(const G1A* pk, con
 // different groups could cancel) and [r_i] pk_i computed from the key's window
 // table; the four digits count into their buckets.
 // (Fused launches of at least l0_duty_partials partials run l0duty::k_rlc_g1_l0
-// below instead.)
-__global__ void TBG_LAUNCH k_rlc_g1_l0(DevBatch B, const G1A* tab, const int32_t* pk_status, uint32_t n_pk) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+// below instead.)  The first n_s workgroups of a fused launch run the S role
+// (0 without the batched subgroup test: the bucket MSM below forms S).
+__global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_rlc_g1_l0(DevBatch B, const G1A* tab, const int32_t* pk_status,
+                                                          uint32_t n_pk, uint32_t n_s) {
+  if (l0f_s_block(B, n_s)) return;
+  const uint32_t i = (blockIdx.x - n_s) * blockDim.x + threadIdx.x;
   if (i >= B.n_partials || B.partial_status[i] != TBG_PS_NOT_VERIFIED) return;
   const uint32_t pid = B.pubkey_ids[i];
   const bool fused = l0_fused(B);
@@ -106,8 +218,10 @@ __global__ void TBG_LAUNCH k_rlc_g1_l0(DevBatch B, const G1A* tab, const int32_t
 // its two table entries).
 namespace l0duty {
 static_assert(BINV_BLOCK == kBlock, "k_rlc_g1_l0: the workgroup of the batched inversion");
-__global__ void TBG_LAUNCH k_rlc_g1_l0(DevBatch B, const G1A* tab, const int32_t* pk_status, uint32_t n_pk) {
-  const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
+__global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_rlc_g1_l0(DevBatch B, const G1A* tab, const int32_t* pk_status,
+                                                          uint32_t n_pk, uint32_t n_s) {
+  if (l0f_s_block(B, n_s)) return;  // (before the workgroup's batched inversion: block-uniform)
+  const uint32_t d = (blockIdx.x - n_s) * blockDim.x + threadIdx.x;
   const bool in = d < B.n_duties;
   uint32_t i0 = 0, n = 0, cand = 0;
   if (in) {
@@ -335,27 +449,29 @@ __global__ void __launch_bounds__(MSM_TREE_WG) k_msm_tree_final(DevBatch B) {
   px_store(*B.batch_pt, Aff<Fp2x>{f_mul(acc.X, zi2), f_mul(acc.Y, f_mul(zi2, zi))});
 }
 
-// ------------------------------------------------------- fused level 0
+// ------------------------------------------ fused level 0, smaller launches
+// Below l0_tail_partials (l0_tail, tbls_launch.h) S keeps its three kernels
+// behind the key side and the aggregation, as before the S role existed.
 // S from the batched subgroup test's sums (bls_rlc.h, top): the 18 columns
 // Qbar_k = sum over the groups of Q_k (k_sgb_combine left Q_k in the first
 // slot of combination k's buckets, k_sgb_test proved it in G2) and the
 // column T (k_sgb_bucket's slice sums), then
 //   S = sum_j psi^j(2 A_j + T),  A_j = sum_e 13^e Qbar_(first_j + e).
-//   k_l0f_reduce  one workgroup per L0F_CHUNK points of a column: their sum
+//   k_l0f_reduce  one workgroup per L0FK_CHUNK points of a column: their sum
 //   k_l0f_fold    one workgroup per column: the sum of its chunk sums
 //   k_l0f_horner  one lane pair per j: A_j by Horner steps, psi^j(2 A_j + T); S affine
 // A failed subgroup group voids level 0 (its Q_k are not in G2 and its
 // members are about to be tested alone: k_sgb.hip sets the flag with
 // sgb_bad), as does a key mark made after the sort (k_rlc_g1_l0) and S = 0.  Every addition takes the complete formulas:
 // small multiples of one point (equal signatures) do meet the doubling case.
-__global__ void __launch_bounds__(2 * L0F_PAIRS) k_l0f_reduce(DevBatch B, uint32_t n_sg, uint32_t wq, uint32_t n_t) {
-  __shared__ Jac<Fp2x> lds[2 * L0F_PAIRS];
+__global__ void __launch_bounds__(2 * L0FK_PAIRS) k_l0f_reduce(DevBatch B, uint32_t n_sg, uint32_t wq, uint32_t n_t) {
+  __shared__ Jac<Fp2x> lds[2 * L0FK_PAIRS];
   if (B.counters[CNT_L0_BAD]) return;  // (grid-uniform: set before this kernel starts)
   const uint32_t pr = threadIdx.x >> 1, b = blockIdx.x;
   const bool qcol = b < SGB_K * wq;
   const uint32_t col = qcol ? b / wq : SGB_K, chunk = qcol ? b % wq : b - SGB_K * wq;
   const uint32_t count = qcol ? n_sg : n_sg * n_t;
-  const uint32_t a0 = chunk * L0F_CHUNK + pr * L0F_PER, a1 = min(a0 + L0F_PER, count);
+  const uint32_t a0 = chunk * L0FK_CHUNK + pr * L0FK_PER, a1 = min(a0 + L0FK_PER, count);
   Jac<Fp2x> acc = jac_inf<Fp2x>();
 #pragma unroll 1
   for (uint32_t a = a0; a < a1; ++a) {  // (pair-uniform)
@@ -365,20 +481,20 @@ __global__ void __launch_bounds__(2 * L0F_PAIRS) k_l0f_reduce(DevBatch B, uint32
       acc = jac_add_in<Fp2x, true>(acc, px_load(B.sgb_t[a]));
     }
   }
-  acc = pair_tree_sum<L0F_PAIRS>(acc, lds);
+  acc = pair_tree_sum<L0FK_PAIRS>(acc, lds);
   if (pr == 0) px_store(B.l0f_sum[b], acc);
 }
 
-__global__ void __launch_bounds__(2 * L0F_PAIRS) k_l0f_fold(DevBatch B, uint32_t wq, uint32_t wt) {
+__global__ void __launch_bounds__(2 * L0FK_PAIRS) k_l0f_fold(DevBatch B, uint32_t wq, uint32_t wt) {
   TBG_URGENT();
-  __shared__ Jac<Fp2x> lds[2 * L0F_PAIRS];
+  __shared__ Jac<Fp2x> lds[2 * L0FK_PAIRS];
   if (B.counters[CNT_L0_BAD]) return;  // (grid-uniform)
   const uint32_t pr = threadIdx.x >> 1, col = blockIdx.x;
   const uint32_t first = col < SGB_K ? col * wq : SGB_K * wq, count = col < SGB_K ? wq : wt;
   Jac<Fp2x> acc = jac_inf<Fp2x>();
 #pragma unroll 1
-  for (uint32_t a = pr; a < count; a += L0F_PAIRS) acc = jac_add_in<Fp2x, true>(acc, px_load(B.l0f_sum[first + a]));
-  acc = pair_tree_sum<L0F_PAIRS>(acc, lds);
+  for (uint32_t a = pr; a < count; a += L0FK_PAIRS) acc = jac_add_in<Fp2x, true>(acc, px_load(B.l0f_sum[first + a]));
+  acc = pair_tree_sum<L0FK_PAIRS>(acc, lds);
   if (pr == 0) px_store(B.l0f_sum[SGB_K * wq + wt + col], acc);
 }
 
@@ -412,14 +528,19 @@ void launch_pubkey_tables(const G1A* pk, const G1A* xpk, const int32_t* status, 
 
 // Level 0's key side: G1 products, bucket sizes, and the ERR_PUBKEY marks
 // (after it the candidates are final: the speculative aggregation may run).
+// With l0_tail(B) a fused launch's grid starts with the S role's workgroups:
+// S is formed beside the key side, before the aggregation and long before
+// k_l0_lines reads it.
 void launch_l0_keys(const DevBatch& B, const G1A* pk_tab, const int32_t* pk_status, uint32_t n_pk, hipStream_t st) {
-  // (msm_off was zeroed by k_decode_sigs, the chain's first kernel)
+  // (msm_off and the S role's counters were zeroed by k_decode_sigs, the chain's first kernel)
+  const uint32_t n_s = l0_tail(B) ? l0f_s_blocks(B) : 0u;
   if (l0_per_duty(B)) {  // P_d and dv_state too; the same name in the per-kernel profile
     using l0duty::k_rlc_g1_l0;
-    TBG_KLAUNCH(k_rlc_g1_l0, grid_for(B.n_duties), dim3(kBlock), st, B, pk_tab, pk_status, n_pk);
+    TBG_KLAUNCH(k_rlc_g1_l0, dim3(n_s + grid_for(B.n_duties).x), dim3(kBlock), st, B, pk_tab, pk_status, n_pk, n_s);
     return;
   }
-  if (B.n_partials) TBG_KLAUNCH(k_rlc_g1_l0, grid_for(B.n_partials), dim3(kBlock), st, B, pk_tab, pk_status, n_pk);
+  if (B.n_partials)
+    TBG_KLAUNCH(k_rlc_g1_l0, dim3(n_s + grid_for(B.n_partials).x), dim3(kBlock), st, B, pk_tab, pk_status, n_pk, n_s);
 }
 
 // Level 0's signature side: the bucket MSM up to S (affine).
@@ -432,12 +553,12 @@ void launch_l0_msm(const DevBatch& B, hipStream_t st) {
   TBG_KLAUNCH(k_msm_tree_final, dim3(1), dim3(MSM_TREE_WG), st, B);
 }
 
-// Fused level 0's signature side: S from the subgroup test's sums.
+// Fused level 0's signature side in launches below l0_tail_partials: S from the subgroup test's sums.
 void launch_l0_fused_s(const DevBatch& B, hipStream_t st) {
   const uint32_t n_sg = sgb_groups(B.n_partials, B.sgb_m), n_t = sgb_t_slices(B.sgb_m);
-  const uint32_t wq = l0f_q_chunks(n_sg), wt = l0f_t_chunks(n_sg, B.sgb_m);
-  TBG_KLAUNCH(k_l0f_reduce, dim3(SGB_K * wq + wt), dim3(2 * L0F_PAIRS), st, B, n_sg, wq, n_t);
-  TBG_KLAUNCH(k_l0f_fold, dim3(L0F_COLS), dim3(2 * L0F_PAIRS), st, B, wq, wt);
+  const uint32_t wq = l0fk_q_chunks(n_sg), wt = l0fk_t_chunks(n_sg, B.sgb_m);
+  TBG_KLAUNCH(k_l0f_reduce, dim3(SGB_K * wq + wt), dim3(2 * L0FK_PAIRS), st, B, n_sg, wq, n_t);
+  TBG_KLAUNCH(k_l0f_fold, dim3(L0F_COLS), dim3(2 * L0FK_PAIRS), st, B, wq, wt);
   TBG_KLAUNCH(k_l0f_horner, dim3(1), dim3(L0F_HORNER_THREADS), st, B, SGB_K * wq + wt);
 }
 

@@ -871,9 +871,10 @@ void launch_rlc_prepare(const DevBatch& B, const G1A* pk_aff, const G1A* pk_tab,
   if (B.rlc_batch) {  // level 0: G1 products, P_d, the signature MSM and S's lines
     launch_l0_keys(B, pk_tab, pk_status, n_pk, st);
     if (after_keys) after_keys(B, st);
-    // S: from the subgroup test's sums while the batched test runs, else the bucket MSM
-    if (l0_fused(B)) launch_l0_fused_s(B, st);
-    else launch_l0_msm(B, st);
+    // S: from the subgroup test's sums while the batched test runs -- the key side has formed it
+    // (l0_tail: the S role of k_rlc_g1_l0's grid) or three kernels do now --, else the bucket MSM
+    if (!l0_fused(B)) launch_l0_msm(B, st);
+    else if (!l0_tail(B)) launch_l0_fused_s(B, st);
     // (a per-duty key side has written P_d and dv_state itself: k_rlc_g1_l0)
     if (!l0_per_duty(B)) TBG_KLAUNCH(k_rlc_duty_sum<DSUM_L0_P>, duty_grid(B), dim3(BINV_BLOCK), st, B);
     // shared messages: one key sum Q_m per distinct message (k_l0msg.hip)

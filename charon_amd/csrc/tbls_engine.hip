@@ -148,6 +148,7 @@ struct tbg_ctx {
   uint32_t sgb_mode = TBG_SGB_AUTO;    // batched subgroup test (tbg_config.subgroup_batch)
   uint32_t express_max = TBG_EXPRESS_PARTIALS;  // batches up to this many partials prefer the express slot
   uint32_t l0_duty_partials = TBG_L0_DUTY_PARTIALS;  // fused level 0: P_d per duty from this many partials (tbg_config.l0_duty_partials)
+  uint32_t l0_tail_partials = TBG_L0_TAIL_PARTIALS;  // fused level 0: S inside the key-side grid from this many partials (tbg_config.l0_tail_partials)
   uint32_t l0_msg_share = TBG_L0_MSG_SHARE;  // fused level 0: per message from this many duties per message (tbg_config.l0_msg_share)
   uint32_t sgb_tri_partials = TBG_SGB_TRI_PARTIALS;  // batched subgroup test: triple schedule from this many partials (tbg_config.sgb_tri_partials)
   uint32_t sgb_tri_m = SGB_TRI_M;                    // its group size (tbg_config.sgb_tri_m)
@@ -268,6 +269,7 @@ int tbg_init(const tbg_config* cfg, tbg_ctx** out) {
   if (cfg) c->sgb_mode = cfg->subgroup_batch;
   if (cfg && cfg->express_partials) c->express_max = cfg->express_partials;
   if (cfg && cfg->l0_duty_partials) c->l0_duty_partials = cfg->l0_duty_partials;
+  if (cfg && cfg->l0_tail_partials) c->l0_tail_partials = cfg->l0_tail_partials;
   if (cfg && cfg->l0_msg_share) c->l0_msg_share = cfg->l0_msg_share;
   if (cfg && cfg->sgb_tri_partials) c->sgb_tri_partials = cfg->sgb_tri_partials;
   if (cfg && cfg->sgb_tri_m) c->sgb_tri_m = cfg->sgb_tri_m;
@@ -1224,6 +1226,7 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   B.l0f_sum = (G2J*)(dw + w_l0fsum);
   B.l0f_u = (uint32_t*)(dw + w_l0fu);
   B.l0_duty_partials = c->l0_duty_partials;
+  B.l0_tail_partials = c->l0_tail_partials;
   B.l0_msg_share = l0m ? c->l0_msg_share : TBG_L0_MSG_NEVER;  // (no plan: never by message)
   B.l0m_n_chunks = l0m ? parts[n_batches - 1].ch1 : 0;
   B.l0m_max_chunks = l0m ? parts[n_batches - 1].maxch : 0;

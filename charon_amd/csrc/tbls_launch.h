@@ -130,6 +130,8 @@ struct DevBatch {
   // that test's sums (l0_fused below; the msm_* arrays are then not allocated);
   // a failure falls through to the group levels
   uint32_t rlc_batch;     // 1: level 0 runs first (every candidate's r_i random, no group lead)
+  uint32_t l0_tail_partials;  // fused launches of at least this many partials form S inside the key-side
+                              // kernel's grid (l0_tail below; only the launchers read it)
   uint64_t* msm_r;        // [n_partials] r_i of the candidates
   uint32_t* msm_off;      // [MSM_BUCKETS + 1] bucket sizes, then their offsets
   uint32_t* msm_cur;      // [MSM_BUCKETS] scatter cursors
@@ -174,8 +176,9 @@ struct DevBatch {
   uint32_t* sgb_bad;      // [n_sg] 1: some combination is outside G2 (members tested alone)
   // fused level 0 (l0_fused below): S from the subgroup test's sums
   G2J* sgb_t;             // [n_sg][sgb_t_slices(sgb_m)] slice sums of the group's unweighted candidates
-  G2J* l0f_sum;           // [l0f_sum_entries] chunk sums of the Q_k columns and of T (k_l0f_reduce), then
-                          // the L0F_COLS column totals (k_l0f_fold)
+  G2J* l0f_sum;           // [l0f_sum_entries] chunk sums of the Q_k columns and of T, then the L0F_COLS
+                          // column totals (the S role of k_rlc_g1_l0, bls_l0tail.h; in launches below
+                          // l0_tail_partials k_l0f_reduce, then k_l0f_fold, with 512-point chunks)
   uint32_t* l0f_u;        // [n_partials][4] the digits u_j of the fused r_i (k_sgb_sort -> k_rlc_g1_l0)
   uint32_t l0_duty_partials;   // fused launches of at least this many partials form P_d per duty (l0_per_duty below)
   // level 0 by message (l0_by_msg below; bls_l0msg.h, k_l0msg.hip): one G1 sum
@@ -208,6 +211,7 @@ struct DevBatch {
   const uint32_t* duty_set;   // [n_duties] the duty's set
   int32_t* set_status;        // [n_sets + SET_TAIL] TBG_SS_* per set (outputs), then SET_BAD, SET_ANY
 };
+static_assert(offsetof(DevBatch, msm_r) == offsetof(DevBatch, rlc_batch) + 8, "l0_tail_partials fills rlc_batch's padding");
 // set_status's tail words: SET_BAD counts the partials left invalid or
 // unverified (every candidate of a failed group: the adaptive policies' upper
 // bound), SET_ANY the partials whose code is not VALID (0: nothing to rewrite)
@@ -219,9 +223,12 @@ enum GroupState : int32_t { GRP_EMPTY = 0, GRP_LINES = 1, GRP_OK = 2, GRP_FAIL =
 // CNT_DUTIES: level-2b duties (id_list), CNT_PARTIALS: level-3 partials, CNT_AGG: [1/D] duties,
 // CNT_CHUNKS: level-1.5 chunks, CNT_CID: level-1.5b chunks, CNT_L0_BAD: level 0 cannot
 // hold (a degenerate sum, a duty checked per partial, an unusable H(m)), CNT_L0_OK: level 0 passed
+// CNT_L0F_COL + col: the chunk sums of column col stored so far, CNT_L0F_DONE: the column totals
+// stored so far (the fused level 0's S role, bls_l0tail.h: the last arriver goes on).  Like every
+// counter they are zeroed by k_decode_sigs at the head of each chain, replays included.
 enum Counter : int { CNT_DUTIES = 0, CNT_PARTIALS = 1, CNT_AGG = 2, CNT_CHUNKS = 3, CNT_CID = 4, CNT_L0_BAD = 5,
-                     CNT_L0_OK = 6, CNT_GID = 7, CNT_LAZY = 8, CNT_WORDS = 9 };  // CNT_GID: level-1g groups,
-                                                                                // CNT_LAZY: gm_list entries
+                     CNT_L0_OK = 6, CNT_GID = 7, CNT_LAZY = 8,  // CNT_GID: level-1g groups, CNT_LAZY: gm_list entries
+                     CNT_L0F_COL = 9, CNT_L0F_DONE = CNT_L0F_COL + 19, CNT_WORDS = CNT_L0F_DONE + 1 };
 
 // Level-0 MSM: a digit a (odd, |a| < 2^16) of r_i puts psi^k(s_i) into bucket
 // (|a| - 1) / 2; the tree sums (k_msm_tree) leave one point per workgroup in
@@ -317,6 +324,13 @@ TBG_HD size_t sgb_q_slot(const DevBatch& B, uint32_t g, uint32_t k) {
                                                  : sgb_paired(B.sgb_m) ? SGB_PBUCKETS + SGB_V * k
                                                                        : SGB_V * k * B.sgb_split);
 }
+// (the same from the two fields alone: the S role of k_rlc_g1_l0 is an out-of-line body that is
+// handed the launch's fields it needs, not the DevBatch)
+TBG_HD size_t sgb_q_slot(uint32_t m, uint32_t split, uint32_t g, uint32_t k) {
+  return (size_t)sgb_part_stride(m) * g + (sgb_triple(m)   ? SGB_TFOLD + SGB_V * k
+                                           : sgb_paired(m) ? SGB_PBUCKETS + SGB_V * k
+                                                           : SGB_V * k * split);
+}
 // Fused level 0 (bls_rlc.h, k_msm.hip): while the batched subgroup test runs,
 // r_i is a fixed linear form of the partial's 18 subgroup digits, so S is a
 // fixed linear form of the test's sums Q_k (summed over the groups) and of the
@@ -354,12 +368,34 @@ TBG_HD bool l0_by_msg(const DevBatch& B) {
 constexpr uint32_t SGB_T_PER = 32;  // candidates per slice of T (no longer a chain than a bucket slice's ~40)
 TBG_HD uint32_t sgb_t_slices(uint32_t m) { return m / SGB_T_PER; }  // (m: a power of two >= SGB_M_MIN = 64)
 constexpr uint32_t L0F_COLS = SGB_K + 1;        // the 18 sums over the groups of Q_k, then T
-constexpr uint32_t L0F_PAIRS = 128, L0F_PER = 4;  // k_l0f_reduce: lane pairs per workgroup, points per pair
+// The S role of k_rlc_g1_l0 (bls_l0tail.h, whose L0T_* constants k_msm.hip checks against
+// these): one wave per chunk -- kBlock / 2 lane pairs, 4 points per pair.  l0f_sum is sized for
+// these chunks; the 512-point chunks of k_l0f_reduce (L0FK_*, smaller launches) need fewer entries.
+constexpr uint32_t L0F_PAIRS = kBlock / 2, L0F_PER = 4;
 constexpr uint32_t L0F_CHUNK = L0F_PAIRS * L0F_PER;
+constexpr uint32_t L0FK_PAIRS = 128, L0FK_PER = 4;  // k_l0f_reduce: lane pairs per workgroup, points per pair
+constexpr uint32_t L0FK_CHUNK = L0FK_PAIRS * L0FK_PER;
+static_assert(L0FK_CHUNK >= L0F_CHUNK, "l0f_sum holds either chunking");
+TBG_HD uint32_t l0fk_q_chunks(uint32_t n_sg) { return (n_sg + L0FK_CHUNK - 1) / L0FK_CHUNK; }
+TBG_HD uint32_t l0fk_t_chunks(uint32_t n_sg, uint32_t m) { return (n_sg * sgb_t_slices(m) + L0FK_CHUNK - 1) / L0FK_CHUNK; }
+static_assert(CNT_L0F_DONE - CNT_L0F_COL == (int)L0F_COLS, "one counter per column");
 TBG_HD uint32_t l0f_q_chunks(uint32_t n_sg) { return (n_sg + L0F_CHUNK - 1) / L0F_CHUNK; }
 TBG_HD uint32_t l0f_t_chunks(uint32_t n_sg, uint32_t m) { return (n_sg * sgb_t_slices(m) + L0F_CHUNK - 1) / L0F_CHUNK; }
 TBG_HD uint32_t l0f_sum_entries(uint32_t n_sg, uint32_t m) {
   return SGB_K * l0f_q_chunks(n_sg) + l0f_t_chunks(n_sg, m) + L0F_COLS;
+}
+// S inside the key-side kernel's grid (bls_l0tail.h) in fused launches of at least
+// l0_tail_partials partials (tbg_config.l0_tail_partials, default TBG_L0_TAIL_PARTIALS = 131,072:
+// 2,048 wave slots x 64 lanes, from where the key side fills every wave slot of the machine and
+// lasts longer than the S chain it hides).  Below it the key side is one wave's chain, shorter
+// than the S chain, which as a role runs out-of-line point operations: nothing would be hidden,
+// and the launch keeps k_l0f_reduce, k_l0f_fold and k_l0f_horner after the aggregation.  A
+// replayed prefix decides from its own partials.  Same S either way.
+TBG_HD bool l0_tail(const DevBatch& B) { return l0_fused(B) && B.n_partials >= B.l0_tail_partials; }
+// the S role's workgroups in such a launch's key-side grid (the lowest block indices)
+TBG_HD uint32_t l0f_s_blocks(const DevBatch& B) {
+  const uint32_t n_sg = sgb_groups(B.n_partials, B.sgb_m);
+  return SGB_K * l0f_q_chunks(n_sg) + l0f_t_chunks(n_sg, B.sgb_m);
 }
 // Level-0 product tree over the groups' P-chunk products.  Each pass is a
 // chain of F - 1 Fp12 products on one lane group (~24 us each at one wave per
@@ -468,11 +504,11 @@ void launch_lines_fold(const DevBatch& B, int kind, uint32_t max_entries, hipStr
 void launch_set_init(const DevBatch& B, hipStream_t st);
 void launch_set_resolve(const DevBatch& B, hipStream_t st);
 void launch_set_status(const DevBatch& B, hipStream_t st);
-// level 0 (k_msm.hip)
+// level 0 (k_msm.hip); with l0_tail(B) a fused launch's key side forms S too (its grid's S role)
 void launch_pubkey_tables(const G1A* pk, const G1A* xpk, const int32_t* status, uint32_t n, G1A* tab, hipStream_t st);
 void launch_l0_keys(const DevBatch& B, const G1A* pk_tab, const int32_t* pk_status, uint32_t n_pk, hipStream_t st);
 void launch_l0_msm(const DevBatch& B, hipStream_t st);
-// fused level 0: S from the subgroup test's sums (k_l0f_reduce, k_l0f_fold, k_l0f_horner)
+// fused level 0 below l0_tail_partials: S from the subgroup test's sums (k_l0f_reduce, k_l0f_fold, k_l0f_horner)
 void launch_l0_fused_s(const DevBatch& B, hipStream_t st);
 void launch_l0_check(const DevBatch& B, hipStream_t st);
 // level 0's P-chunk and S Miller products on hexads (k_miller_hex.hip)

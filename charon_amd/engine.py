@@ -33,6 +33,7 @@ SGB_AUTO, SGB_ON, SGB_OFF = 0, 1, 2           # tbg_config.subgroup_batch
 SGB_SCHEDULES = ("none", "classic", "paired", "triple")  # TBG_SGB_SCHED_* (tbg_fetch_subgroup_schedule)
 EXPRESS_OFF = 0xFFFFFFFF                        # tbg_config.express_partials: no express slot
 L0_DUTY_ALWAYS, L0_DUTY_NEVER = 1, 0xFFFFFFFF   # tbg_config.l0_duty_partials (0: TBG_L0_DUTY_PARTIALS)
+L0_TAIL_ALWAYS, L0_TAIL_NEVER = 1, 0xFFFFFFFF   # tbg_config.l0_tail_partials (0: TBG_L0_TAIL_PARTIALS)
 SGB_TRI_NEVER = 0xFFFFFFFF                      # tbg_config.sgb_tri_partials (0: TBG_SGB_TRI_PARTIALS)
 L0_MSG_ALWAYS, L0_MSG_NEVER = 1, 0xFFFFFFFF     # tbg_config.l0_msg_share (0: TBG_L0_MSG_SHARE duties per message)
 L0_NOT_RUN, L0_PASSED, L0_FAILED = 0, 1, 2     # tbg_fetch_level0
@@ -109,14 +110,15 @@ class Engine:
                  rlc_seed: int = 0, rlc_chunk: int = 0, streams_per_slot: int = 0, rlc_batch: int = 0,
                  gident: int = GIDENT_OFF, fb_window: int = 0, subgroup_batch: int = SGB_AUTO,
                  express_partials: int = 0, l0_duty_partials: int = 0, l0_msg_share: int = 0,
-                 sgb_tri_partials: int = 0, sgb_tri_m: int = 0):
+                 sgb_tri_partials: int = 0, sgb_tri_m: int = 0, l0_tail_partials: int = 0):
         self._lib = _native.load()
         cfg = _native.TbgConfig(device=device, max_partials=0, max_duties=0, max_msg_bytes=0, slots=slots,
                                 verify_mode=verify_mode, rlc_group=rlc_group, rlc_seed=rlc_seed,
                                 rlc_chunk=rlc_chunk, streams_per_slot=streams_per_slot, rlc_batch=rlc_batch,
                                 gident=gident, fb_window=fb_window, subgroup_batch=subgroup_batch,
                                 express_partials=express_partials, l0_duty_partials=l0_duty_partials,
-                                l0_msg_share=l0_msg_share, sgb_tri_partials=sgb_tri_partials, sgb_tri_m=sgb_tri_m)
+                                l0_msg_share=l0_msg_share, sgb_tri_partials=sgb_tri_partials, sgb_tri_m=sgb_tri_m,
+                                l0_tail_partials=l0_tail_partials)
         h = ctypes.c_void_p()
         rc = self._lib.tbg_init(ctypes.byref(cfg), ctypes.byref(h))
         self._check(rc, "tbg_init")

@@ -155,7 +155,16 @@ typedef struct {
                            * 0 -> TBG_SGB_TRI_PARTIALS, TBG_SGB_TRI_NEVER -> never       */
   uint32_t sgb_tri_m;     /* its group size: a power of two, 2,048 .. 32,768
                            * (0 -> the compiled default, 16,384)                       */
+  uint32_t l0_tail_partials; /* level 0 with the batched subgroup test on: device batches
+                           * of at least this many partials form S in the first
+                           * workgroups of the key-side kernel's own grid, beside the key
+                           * side; smaller ones, whose key side is shorter than the S
+                           * chain, keep the three S kernels behind it.  Same results
+                           * either way.  0 -> TBG_L0_TAIL_PARTIALS, 1 -> always,
+                           * TBG_L0_TAIL_NEVER -> never                                */
 } tbg_config;
+#define TBG_L0_TAIL_PARTIALS 131072u
+#define TBG_L0_TAIL_NEVER 0xFFFFFFFFu
 #define TBG_SGB_TRI_PARTIALS 262144u
 #define TBG_SGB_TRI_NEVER 0xFFFFFFFFu
 #define TBG_L0_MSG_SHARE 2u

@@ -180,12 +180,14 @@ def main():
                           + l0_per_launch / launch_dvs)
     # the bucket-MSM chain with the batched subgroup test (before the fused level 0)
     unit_3of4_l0_msm = unit_3of4_l0_alone - 4 * decode + 4 * decode_sgb
-    # Fused level 0 (round 7; bls_rlc.h top, k_msm.hip k_l0f_*): with the
+    # Fused level 0 (round 7; bls_rlc.h top, bls_l0tail.h): with the
     # batched subgroup test on, S comes from that test's sums.  Per partial:
     # one more mixed addition (the unweighted sum T, k_sgb_bucket) and the
     # 10 + 8-window key product (no bucket additions); per launch the sums of
-    # the 18 Q_k slots and T's slices over the groups (k_l0f_reduce / _fold:
-    # one addition per point) and the Horner chain (k_l0f_horner).  Probes:
+    # the 18 Q_k slots and T's slices over the groups (one addition per
+    # point) and the Horner chain -- since round 16, in launches of at least
+    # TBG_L0_TAIL_PARTIALS partials, the S role of k_rlc_g1_l0's own grid, a
+    # per-launch term of that kernel; k_l0f_* in smaller launches.  Probes:
     # tests/l0fused/l0fused_host.cpp built with TBG_COUNT_OPS.
     fsrc = os.path.join(ROOT, "tests", "l0fused", "l0fused_host.cpp")
     flib_path = os.path.join(ROOT, "tests", "l0fused", "libl0fused_count.so")
@@ -305,11 +307,15 @@ def main():
             # profiles a 16-batch launch, 640,000 partials.  A smaller launch (the driver shape's 7 + 7 + 6
             # batches, config 4, a lone batch) runs k_rlc_g1_l0_per_partial and k_rlc_duty_sum<DSUM_L0_P>:
             # price its kernel with those two entries and its unit with unit_3of4_l0_per_partial_form.
-            "k_rlc_g1_l0": {"per": "duty", "mads": round(l0f_duty4), "from_partials_per_launch": L0_DUTY_PARTIALS},
+            # From TBG_L0_TAIL_PARTIALS = 131,072 partials per launch either form's grid also holds the S role
+            # (bls_l0tail.h): the column sums and the Horner chain, per launch.  Smaller launches run k_l0f_* instead.
+            "k_rlc_g1_l0": {"per": "duty", "mads": round(l0f_duty4), "from_partials_per_launch": L0_DUTY_PARTIALS,
+                            "plus_per_launch": round(l0f_reduce) + l0f_horner},
             "k_rlc_g1_l0_per_partial": {"per": "partial", "mads": round(l0f_g1),
-                                        "below_partials_per_launch": L0_DUTY_PARTIALS},
-            "k_l0f_reduce": {"per": "launch", "mads": round(l0f_reduce)},
-            "k_l0f_horner": {"per": "launch", "mads": l0f_horner},
+                                        "below_partials_per_launch": L0_DUTY_PARTIALS,
+                                        "plus_per_launch": round(l0f_reduce) + l0f_horner},
+            "k_l0f_reduce": {"per": "launch", "mads": round(l0f_reduce), "below_partials_per_launch": 131072},
+            "k_l0f_horner": {"per": "launch", "mads": l0f_horner, "below_partials_per_launch": 131072},
             # without the batched subgroup test: the bucket MSM (k_rlc_g1_l0 then costs k_rlc_g1_l0_msm)
             "k_rlc_g1_l0_msm": {"per": "partial", "mads": round(k_g1_l0)},
             "k_msm_bucket_part": {"per": "partial", "mads": round(4 * k_msm_entry)},
