@@ -79,6 +79,7 @@ __device__ void agg_emit(const DevBatch& B, uint32_t d, const G2J& acc) {
     B.duty_status[d] = TBG_DS_AGG_IDENTITY;
     return;
   }
+  if (B.agg_aff) B.agg_aff[d] = a;  // (grid-uniform: the aggregate's check reads it, k_aggver.hip)
   agg_store_compressed(B, d, a);
   B.duty_status[d] = TBG_DS_OK;
 }
@@ -233,6 +234,7 @@ __global__ void __launch_bounds__(BINV_BLOCK, TBG_PAIR_WAVES) k_aggregate(DevBat
   const Fp2x zi2 = f_sqr(zi);
   const G2A a = {px_gather(f_mul(acc.X, zi2)), px_gather(f_mul(acc.Y, f_mul(zi2, zi)))};
   if (lead) {
+    if (B.agg_aff) B.agg_aff[d] = a;  // (grid-uniform, as in agg_emit)
     agg_store_compressed(B, d, a);
     B.duty_status[d] = TBG_DS_OK;
   }

@@ -478,9 +478,17 @@ static void spec_aggregation(const DevBatch& B, hipStream_t st) {
 // several slots enqueues stage 0 of every slot before stage 1 of any, so the
 // slots' first kernels start together instead of one chain's enqueue time
 // (~100 launches) apart.
+// TBG_OP_AGGREGATE_VERIFY: the recombination is on the path -- decode,
+// lagrange (ev[8]), aggregate (ev[9]), then the checks of the batch's view V
+// (aggver_view: one candidate per duty, the affine aggregate), whose key side
+// ends at ev[2]; after the join, V's check levels and their verdicts as duty
+// codes, ev[6] to ev[7], the chain's end (chain_end).  The per-message chain
+// runs on st2 beside all of it.  Nothing is speculative.
 static int launch_chain(tbg_ctx* c, const Slot& sl, const DevBatch& B, hipEvent_t* ev, int stage = -1) {
   hipStream_t st = sl.st, st2 = sl.st2;
   const bool verify = B.op != TBG_OP_AGGREGATE;
+  const bool aggver = B.op == TBG_OP_AGGREGATE_VERIFY;
+  const DevBatch V = checked_batch(B);  // (B itself but for TBG_OP_AGGREGATE_VERIFY)
   const G1A* pk = (const G1A*)c->d_pk;
   // With one stream per slot the two independent chains run one after the
   // other, the per-message chain first (running the per-signature chain
@@ -502,6 +510,17 @@ static int launch_chain(tbg_ctx* c, const Slot& sl, const DevBatch& B, hipEvent_
     HIP_TRY(hipEventRecord(ev[10], st));
     launch_decode_sigs(B, st);  // zeroes B.counters (and level 0's bucket sizes) first
     HIP_TRY(hipEventRecord(ev[1], st));
+    if (aggver) {
+      launch_lagrange(B, st);
+      HIP_TRY(hipEventRecord(ev[8], st));
+      launch_aggregate(B, st);
+      launch_aggregate_finish(B, st);
+      HIP_TRY(hipEventRecord(ev[9], st));
+      launch_aggver_candidates(B, V, st);  // zeroes V.counters (and level 0's bucket sizes) first
+      launch_rlc_prepare(V, pk, (const G1A*)c->d_pktab, (const int32_t*)c->d_pk_status, c->n_pk, st);
+      HIP_TRY(hipEventRecord(ev[2], st));
+      return TBG_OK;
+    }
     // The aggregation a level-0 pass will confirm runs as soon as the
     // candidates are final (after the key checks), before the bucket MSM:
     // placed after it, its small kernels waited behind the other launches'
@@ -525,6 +544,13 @@ static int launch_chain(tbg_ctx* c, const Slot& sl, const DevBatch& B, hipEvent_
   if (stage >= 0 && stage != 2) return TBG_OK;
   HIP_TRY(hipStreamWaitEvent(st, ev[5], 0));
   HIP_TRY(hipEventRecord(ev[6], st));
+  if (aggver) {
+    launch_rlc_check(V, pk, (const G1A*)c->d_pktab, (const int32_t*)c->d_pk_status, c->n_pk, st);
+    launch_aggver_status(B, V, st);
+    HIP_TRY(hipEventRecord(ev[7], st));
+    HIP_TRY(hipGetLastError());
+    return TBG_OK;
+  }
   if (verify) launch_rlc_check(B, pk, (const G1A*)c->d_pktab, (const int32_t*)c->d_pk_status, c->n_pk, st);
   HIP_TRY(hipEventRecord(ev[7], st));
   if (B.op != TBG_OP_VERIFY) launch_lagrange(B, st);
@@ -536,21 +562,25 @@ static int launch_chain(tbg_ctx* c, const Slot& sl, const DevBatch& B, hipEvent_
   return TBG_OK;
 }
 
+// The event a chain ends with (launch_chain).
+static int chain_end(uint32_t op) { return op == TBG_OP_AGGREGATE_VERIFY ? 7 : 9; }
+
 // [decode, hash, combine, H lines, verify, lagrange, aggregate, total]
-static void chain_times(hipEvent_t* e, float* ms) {
+static void chain_times(hipEvent_t* e, float* ms, uint32_t op) {
+  const bool aggver = op == TBG_OP_AGGREGATE_VERIFY;  // (the recombination before the checks)
   hipEventElapsedTime(&ms[0], e[10], e[1]);
   hipEventElapsedTime(&ms[1], e[3], e[4]);
-  hipEventElapsedTime(&ms[2], e[1], e[2]);
+  hipEventElapsedTime(&ms[2], e[aggver ? 9 : 1], e[2]);
   hipEventElapsedTime(&ms[3], e[4], e[5]);
   hipEventElapsedTime(&ms[4], e[6], e[7]);
-  hipEventElapsedTime(&ms[5], e[7], e[8]);
+  hipEventElapsedTime(&ms[5], e[aggver ? 1 : 7], e[8]);
   hipEventElapsedTime(&ms[6], e[8], e[9]);
-  hipEventElapsedTime(&ms[7], e[0], e[9]);
+  hipEventElapsedTime(&ms[7], e[0], e[chain_end(op)]);
 }
 
 static int validate(const tbg_batch* b) {
   if (!b) return TBG_E_INVALID_ARG;
-  if (b->op < TBG_OP_VERIFY || b->op > TBG_OP_VERIFY_AGGREGATE) return TBG_E_INVALID_ARG;
+  if (b->op < TBG_OP_VERIFY || b->op > TBG_OP_AGGREGATE_VERIFY) return TBG_E_INVALID_ARG;
   if (b->n_duties == 0) return TBG_E_INVALID_ARG;
   if (!b->duty_first || (b->n_partials && (!b->sigs || !b->identifiers))) return TBG_E_INVALID_ARG;
   if (b->duty_first[0] != 0 || b->duty_first[b->n_duties] != b->n_partials) return TBG_E_INVALID_ARG;
@@ -559,6 +589,8 @@ static int validate(const tbg_batch* b) {
     if (b->duty_first[d + 1] - b->duty_first[d] > 255) return TBG_E_INVALID_ARG;
   }
   if (b->op != TBG_OP_AGGREGATE) {
+    // (pubkey_ids: [n_partials]; under TBG_OP_AGGREGATE_VERIFY [n_duties], one group key per
+    // duty -- required either way; duty_threshold is not read under that op)
     if (!b->msg_off || !b->duty_msg || !b->pubkey_ids || b->n_msgs == 0) return TBG_E_INVALID_ARG;
     if (b->msg_off[0] != 0) return TBG_E_INVALID_ARG;
     for (uint32_t m = 0; m < b->n_msgs; ++m)
@@ -750,6 +782,11 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   }
   const uint32_t op = bs[0]->op;
   const bool verify = op != TBG_OP_AGGREGATE;
+  // TBG_OP_AGGREGATE_VERIFY: the checks run on the batch's view (aggver_view), one
+  // candidate per duty, so every array of the check levels is sized by duties (vp below)
+  // and the per-duty key ids are packed by duty count
+  const bool aggver = op == TBG_OP_AGGREGATE_VERIFY;
+  if (aggver && set_first) return TBG_E_INVALID_ARG;
   uint64_t nd64 = 0, np64 = 0, nm64 = 0, mb64 = 0;
   for (uint32_t k = 0; k < n_batches; ++k) {
     nd64 += bs[k]->n_duties;
@@ -789,6 +826,7 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
     if (nd64 > 0x7FFFFFFFull) return TBG_E_INVALID_ARG;
   }
   const uint32_t nd = (uint32_t)nd64;
+  const uint32_t vp = aggver ? nd : np;  // candidates of the check levels
 
   // ---- input arena layout (16-byte aligned sections) ----
   size_t o = 0;
@@ -801,8 +839,9 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   size_t o_pduty = sec(4ull * np);
   size_t o_sigs = sec(96ull * np);
   size_t o_ids = sec(np);
-  size_t o_pk = sec(4ull * np);
+  size_t o_pk = sec(4ull * vp);
   size_t o_dset = sec(set_first ? 4ull * nd : 0);
+  size_t o_iota = sec(aggver ? 4ull * (nd + 1) : 0);
   // Level 0 by message (bls_l0msg.h): the duties sorted by message and the
   // chunk plan, packed with the inputs.  Reserved whenever a fused level 0
   // may run with the knob on, whatever the launch's own duties per message:
@@ -812,7 +851,7 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   // Nothing is reserved or sorted when no prefix of the caller batches
   // reaches the share (one message per duty: the headline workload).
   bool l0m_in = false;
-  if (verify && c->rlc_group != 0 && c->rlc_batch != TBG_RLC_L0_OFF && c->sgb_mode != TBG_SGB_OFF &&
+  if (verify && !aggver && c->rlc_group != 0 && c->rlc_batch != TBG_RLC_L0_OFF && c->sgb_mode != TBG_SGB_OFF &&
       c->l0_msg_share != TBG_L0_MSG_NEVER && np >= SGB_MIN_PARTIALS) {
     uint64_t cd = 0, cm = 0;
     for (uint32_t k = 0; k < n_batches; ++k) {
@@ -837,12 +876,12 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   // The fallback levels' lines share one buffer of fb_w list positions,
   // consumed in passes (DevBatch::fb_window): a slot no longer holds 22.8 KB
   // per partial for lists that a clean batch leaves empty.
-  const uint32_t fb_w = verify ? std::max<uint32_t>(1u, std::min<uint32_t>(c->fb_window, np)) : 0u;
+  const uint32_t fb_w = verify ? std::max<uint32_t>(1u, std::min<uint32_t>(c->fb_window, vp)) : 0u;
   size_t w_sl = sec(4ull * LINES_WORDS * fb_w);
   size_t w_hl = sec(4ull * LINES_WORDS * nm);
   // Level 0 while the collected batches are clean (or as configured): one
   // failed level-0 check costs its own work on top of the group levels.
-  const bool l0 = G != 0 && np < (1u << 28) &&
+  const bool l0 = G != 0 && vp < (1u << 28) &&
                   (c->rlc_batch == TBG_RLC_L0_ON || (c->rlc_batch == TBG_RLC_L0_AUTO && c->invalid_ema < TBG_RLC_AUTO_L0));
   uint32_t C = c->rlc_chunk;
   // (a set launch keeps its G: the sets are padded to it)
@@ -850,8 +889,8 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   if (C > G) C = G ? G : 1;
   const uint32_t ng = G ? (nd + G - 1) / G : 0;
   const uint32_t nch = G ? (G + C - 1) / C : 0;
-  size_t w_pp = sec(G ? sizeof(G1J) * (size_t)np : 0);
-  size_t w_ps = sec(G ? sizeof(G2J) * (size_t)np : 0);
+  size_t w_pp = sec(G ? sizeof(G1J) * (size_t)vp : 0);
+  size_t w_ps = sec(G ? sizeof(G2J) * (size_t)vp : 0);
   size_t w_cf = sec(G ? 4ull * 3 * 4 * NL * ng * (nch + 1) : 0);
   size_t w_cl = sec(G > 1 ? 4ull * ng * nch : 0);
 
@@ -861,7 +900,7 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   size_t w_gst = sec(4ull * ng);
   size_t w_gl = sec(4ull * LINES_WORDS * ng);
   size_t w_cnt = sec(4ull * CNT_WORDS);
-  size_t w_pl = sec(verify ? 4ull * np : 0);
+  size_t w_pl = sec(verify ? 4ull * vp : 0);
   size_t w_dvfe = sec(G > 1 ? 4ull * 3 * 4 * NL * nd : 0);
   size_t w_pend = sec(G ? sizeof(G2A) * (size_t)std::max<size_t>(std::max<size_t>(ng, (size_t)ng * nch), nd) : 0);
   size_t w_cfe = sec(G > 1 ? 4ull * 3 * 4 * NL * ng * nch : 0);
@@ -880,10 +919,10 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   size_t w_gf = sec(l0 ? 4ull * 3 * 4 * NL * grp_f_entries(ng) : 0);
   // level 1's group MSM (k_gmsm.hip): entries, offsets, bucket sums, leads, the failed groups' candidates
   size_t w_gmoff = sec(G ? 4ull * (GM_BUCKETS + 1) * ng : 0);
-  size_t w_gment = sec(G ? 64ull * np : 0);
+  size_t w_gment = sec(G ? 64ull * vp : 0);
   size_t w_gmpart = sec(G ? sizeof(G2J) * GM_BUCKETS * (size_t)ng : 0);
   size_t w_gmlead = sec(G ? 4ull * ng : 0);
-  size_t w_gmlist = sec(G ? 4ull * np : 0);
+  size_t w_gmlist = sec(G ? 4ull * vp : 0);
   size_t w_gmhist = sec(G ? 4ull * 256 : 0);
   size_t w_gmorder = sec(G ? 4ull * GM_BUCKETS * ng : 0);
   // Batched subgroup test while the collected batches carry (almost) no
@@ -915,12 +954,14 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   // test's sums (l0_fused, tbls_launch.h; a replayed prefix of the launch
   // keeps both flags, so it takes the same path) and the bucket MSM's
   // arrays are not needed; otherwise the bucket MSM of k_msm.hip.
-  const bool fused = l0 && sgb;
+  // (TBG_OP_AGGREGATE_VERIFY: the subgroup test is the partials', the level 0 the view's,
+  // which has no digits to take S from -- always the bucket MSM, over the duties)
+  const bool fused = l0 && sgb && !aggver;
   const bool msm = l0 && !fused;
-  size_t w_mr = sec(msm ? 8ull * np : 0);
+  size_t w_mr = sec(msm ? 8ull * vp : 0);
   size_t w_moff = sec(msm ? 4ull * (MSM_BUCKETS + 1) : 0);
   size_t w_mcur = sec(msm ? 4ull * MSM_BUCKETS : 0);
-  size_t w_ment = sec(msm ? 16ull * np : 0);
+  size_t w_ment = sec(msm ? 16ull * vp : 0);
   size_t w_mbkt = sec(msm ? sizeof(G2J) * (size_t)MSM_BUCKETS : 0);
   size_t w_mpart = sec(msm ? sizeof(G2J) * (size_t)MSM_BUCKETS * MSM_SPLIT : 0);
   size_t w_msum = sec(msm ? sizeof(G2J) * (size_t)MSM_SUM_ENTRIES : 0);
@@ -937,6 +978,9 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   size_t w_l0mst = sec(l0m ? 4ull * nm : 0);
   size_t w_aacc = sec(op != TBG_OP_VERIFY ? sizeof(G2J) * (size_t)nd : 0);
   size_t w_alist = sec(op != TBG_OP_VERIFY ? 4ull * nd : 0);
+  size_t w_aaff = sec(aggver ? sizeof(G2A) * (size_t)nd : 0);
+  size_t w_avst = sec(aggver ? 4ull * nd : 0);
+  size_t w_avcnt = sec(aggver ? 4ull * CNT_WORDS : 0);
   size_t w_out = o;  // outputs are contiguous so one D2H copy brings them back
   size_t w_pst = sec(4ull * np);
   size_t w_dst = sec(4ull * nd);
@@ -994,7 +1038,8 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
       if (bmb) memcpy(h + o_msgs + MB, b->msgs, bmb);
       for (uint32_t m = 0; m < bnm; ++m) msg_off[M + m] = MB + b->msg_off[m];
       for (uint32_t d = 0; d < bnd; ++d) duty_msg[D + d] = M + b->duty_msg[d];
-      memcpy(h + o_pk + 4ull * P, b->pubkey_ids, 4ull * bnp);
+      if (aggver) memcpy(h + o_pk + 4ull * D, b->pubkey_ids, 4ull * bnd);  // (one group key per duty)
+      else memcpy(h + o_pk + 4ull * P, b->pubkey_ids, 4ull * bnp);
       if (l0m) {  // this batch's duties by message (sections disjoint from the other batches')
         std::vector<uint32_t> cursor(bnm);
         l0m_sort_batch(duty_msg, D, bnd, M, bnm, (uint32_t*)(h + o_mfirst), (uint32_t*)(h + o_mduty), cursor.data());
@@ -1065,6 +1110,8 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   }
   duty_first[nd] = np;
   if (verify) msg_off[nm] = MB;
+  if (aggver)
+    for (uint32_t d = 0; d <= nd; ++d) ((uint32_t*)(h + o_iota))[d] = d;
   // Level 0 by message, the chunk plan (chunk -> message, message -> first
   // chunk; the shape of SumPlan, k_sum.hip).  Invariant: the messages of
   // caller batch j follow those of batch j - 1 and a message never spans
@@ -1115,7 +1162,7 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   B.lam = (uint32_t*)(dw + w_lam);
   B.sig_lines = (uint32_t*)(dw + w_sl);
   B.h_lines = (uint32_t*)(dw + w_hl);
-  B.rlc_group = G;
+  B.rlc_group = aggver ? 0u : G;  // (the batch itself runs no check: its view does, av_group)
   {
     uint64_t k[4];
     if (c->rlc_seed) {
@@ -1179,7 +1226,7 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
     // batches' invalid share makes likely (10x margin), every pass for the
     // per-partial schedule
     const double share = std::min(1.0, 10.0 * c->invalid_ema);
-    const uint64_t expect = (uint64_t)((double)np * share);
+    const uint64_t expect = (uint64_t)((double)vp * share);
     B.fb_full = (G == 0 || fb_w == 0) ? 0xFFFFFFFFu
                                       : (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (expect / fb_w + 1) * (uint64_t)fb_w);
   }
@@ -1194,7 +1241,16 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
     B.set_status = (int32_t*)(dw + w_sst);
     B.gident = 0;  // (no level 1g: a failed group is not narrowed)
   }
-  B.rlc_batch = l0 ? 1u : 0u;
+  B.rlc_batch = l0 && !aggver ? 1u : 0u;
+  if (aggver) {
+    B.agg_aff = (G2A*)(dw + w_aaff);
+    B.av_status = (int32_t*)(dw + w_avst);
+    B.av_counters = (uint32_t*)(dw + w_avcnt);
+    B.av_iota = (const uint32_t*)(di + o_iota);
+    B.av_group = G;
+    B.av_chunk = C;
+    B.av_batch = l0 ? 1u : 0u;
+  }
   B.msm_r = (uint64_t*)(dw + w_mr);
   B.msm_off = (uint32_t*)(dw + w_moff);
   B.msm_cur = (uint32_t*)(dw + w_mcur);
@@ -1362,6 +1418,16 @@ static int collect_impl(tbg_ctx* c, tbg_ticket t, int32_t* pst, int32_t* dst, ui
     // under bad partials
     s->seen_bad += (uint32_t)((const int32_t*)(s->h_out + s->o_sets))[s->n_sets + SET_BAD];
     s->seen_total += q->np;
+  } else if (s->op == TBG_OP_AGGREGATE_VERIFY) {  // the duties whose aggregate failed, over the duties checked
+    const int32_t* ds = (const int32_t*)(s->h_out + align_up(4ull * s->n_partials, 16));  // (copy_part's layout)
+    uint32_t bad = 0, checked = 0;
+    for (uint32_t d = 0; d < q->nd; ++d) {
+      const int32_t v = ds[q->d0 + d];
+      bad += v == TBG_DS_AGG_INVALID ? 1u : 0u;
+      checked += v == TBG_DS_AGG_INVALID || v == TBG_DS_OK ? 1u : 0u;
+    }
+    s->seen_bad += bad;
+    s->seen_total += checked;
   } else if (s->op != TBG_OP_AGGREGATE && q->np) {  // the adaptive group size's and level 0's input
     const int32_t* st = (const int32_t*)s->h_out;  // partial statuses lead the output region
     uint32_t bad = 0;
@@ -1380,7 +1446,7 @@ static int collect_impl(tbg_ctx* c, tbg_ticket t, int32_t* pst, int32_t* dst, ui
   c->host[5] += q->np;
   c->host[6] += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() -
                                                                                t_gather).count();
-  chain_times(s->ev, s->ms);
+  chain_times(s->ev, s->ms, s->op);
   memcpy(c->last_ms, s->ms, sizeof(c->last_ms));
   part_done(s, q);
   // One update per DEVICE batch, over all of its parts (whatever order they
@@ -1491,13 +1557,13 @@ int tbg_replay_plan(tbg_ctx* c, const tbg_ticket* tickets, const uint32_t* n_par
   if (rc == TBG_OK) {
     for (uint32_t k = 0; k < n_launches; ++k) {
       float m[8];
-      chain_times(ev.data() + (size_t)kChainEvents * k, m);
+      chain_times(ev.data() + (size_t)kChainEvents * k, m, bs[k].op);
       for (int j = 0; j < 7; ++j) acc[j] += m[j];
     }
     // wall time: first launch's start to the latest chain end
     for (uint32_t k = 0; k < n_launches; ++k) {
       float w = 0;
-      hipEventElapsedTime(&w, ev[0], ev[(size_t)kChainEvents * k + 9]);
+      hipEventElapsedTime(&w, ev[0], ev[(size_t)kChainEvents * k + chain_end(bs[k].op)]);
       if (w > acc[7]) acc[7] = w;
     }
     if (ms8) memcpy(ms8, acc, sizeof(acc));
@@ -1581,15 +1647,16 @@ int tbg_fetch_stats(tbg_ctx* c, tbg_ticket t, uint32_t* out4) {
   if (!s) return TBG_E_TICKET;
   HIP_TRY(hipSetDevice(c->device));
   uint32_t cnt[CNT_WORDS] = {};
+  const DevBatch L = checked_batch(s->last);  // (TBG_OP_AGGREGATE_VERIFY: the aggregates' checks)
   if (s->op != TBG_OP_AGGREGATE) {
-    HIP_TRY(hipMemcpyAsync(cnt, s->last.counters, sizeof(cnt), hipMemcpyDeviceToHost, s->st));
+    HIP_TRY(hipMemcpyAsync(cnt, L.counters, sizeof(cnt), hipMemcpyDeviceToHost, s->st));
     HIP_TRY(hipStreamSynchronize(s->st));
   }
-  uint32_t ng = s->last.rlc_group ? (s->last.n_duties + s->last.rlc_group - 1) / s->last.rlc_group : 0;
+  uint32_t ng = L.rlc_group ? (L.n_duties + L.rlc_group - 1) / L.rlc_group : 0;
   out4[0] = ng;
   out4[1] = cnt[CNT_DUTIES];
   out4[2] = cnt[CNT_PARTIALS];
-  out4[3] = s->last.rlc_group;
+  out4[3] = L.rlc_group;
   return TBG_OK;
 }
 
@@ -1600,18 +1667,19 @@ int tbg_fetch_fallback(tbg_ctx* c, tbg_ticket t, uint32_t* out8) {
   if (!s) return TBG_E_TICKET;
   HIP_TRY(hipSetDevice(c->device));
   uint32_t cnt[CNT_WORDS] = {};
+  const DevBatch L = checked_batch(s->last);  // (TBG_OP_AGGREGATE_VERIFY: the aggregates' checks)
   if (s->op != TBG_OP_AGGREGATE) {
-    HIP_TRY(hipMemcpyAsync(cnt, s->last.counters, sizeof(cnt), hipMemcpyDeviceToHost, s->st));
+    HIP_TRY(hipMemcpyAsync(cnt, L.counters, sizeof(cnt), hipMemcpyDeviceToHost, s->st));
     HIP_TRY(hipStreamSynchronize(s->st));
   }
-  out8[0] = s->last.rlc_group ? (s->last.n_duties + s->last.rlc_group - 1) / s->last.rlc_group : 0;
+  out8[0] = L.rlc_group ? (L.n_duties + L.rlc_group - 1) / L.rlc_group : 0;
   out8[1] = cnt[CNT_GID];
   out8[2] = cnt[CNT_CHUNKS];
   out8[3] = cnt[CNT_CID];
   out8[4] = cnt[CNT_DUTIES];
   out8[5] = cnt[CNT_PARTIALS];
-  out8[6] = s->last.rlc_group;
-  out8[7] = s->op == TBG_OP_AGGREGATE || !s->last.rlc_batch ? (uint32_t)TBG_L0_NOT_RUN
+  out8[6] = L.rlc_group;
+  out8[7] = s->op == TBG_OP_AGGREGATE || !L.rlc_batch ? (uint32_t)TBG_L0_NOT_RUN
             : cnt[CNT_L0_OK]                              ? (uint32_t)TBG_L0_PASSED
                                                           : (uint32_t)TBG_L0_FAILED;
   return TBG_OK;
@@ -1622,10 +1690,11 @@ int tbg_fetch_shape(tbg_ctx* c, tbg_ticket t, uint32_t* out4) {
   std::lock_guard<std::mutex> lk(c->mu);
   Slot* s = find_ticket(c, t, false, nullptr);
   if (!s) return TBG_E_TICKET;
-  const uint32_t G = s->last.rlc_group, C = s->last.rlc_chunk;
+  const DevBatch L = checked_batch(s->last);  // (TBG_OP_AGGREGATE_VERIFY: the aggregates' checks)
+  const uint32_t G = L.rlc_group, C = L.rlc_chunk;
   out4[0] = G;
   out4[1] = G ? C : 0;
-  out4[2] = s->last.rlc_batch ? 1u : 0u;
+  out4[2] = L.rlc_batch ? 1u : 0u;
   out4[3] = G ? ((s->last.n_duties + G - 1) / G) * ((G + C - 1) / C) : 0;
   return TBG_OK;
 }
@@ -1683,7 +1752,7 @@ int tbg_fetch_level0_msgs(tbg_ctx* c, tbg_ticket t, uint32_t* out2) {
   Slot* s = find_ticket(c, t, false, nullptr);
   if (!s) return TBG_E_TICKET;
   // (the launch's own fields: launch_rlc_check took its path from the same ones)
-  const DevBatch& B = s->last;
+  const DevBatch B = checked_batch(s->last);  // (TBG_OP_AGGREGATE_VERIFY: never by message)
   out2[0] = out2[1] = 0;
   if (s->op == TBG_OP_AGGREGATE || !B.rlc_batch || !B.rlc_group || !B.n_duties) return TBG_OK;
   const bool by_msg = l0_by_msg(B);
@@ -1699,10 +1768,11 @@ int tbg_fetch_level0(tbg_ctx* c, tbg_ticket t, int32_t* state) {
   Slot* s = find_ticket(c, t, false, nullptr);
   if (!s) return TBG_E_TICKET;
   *state = TBG_L0_NOT_RUN;
-  if (s->op == TBG_OP_AGGREGATE || !s->last.rlc_batch) return TBG_OK;
+  const DevBatch L = checked_batch(s->last);  // (TBG_OP_AGGREGATE_VERIFY: the aggregates' checks)
+  if (s->op == TBG_OP_AGGREGATE || !L.rlc_batch) return TBG_OK;
   HIP_TRY(hipSetDevice(c->device));
   uint32_t cnt[CNT_WORDS] = {};
-  HIP_TRY(hipMemcpyAsync(cnt, s->last.counters, sizeof(cnt), hipMemcpyDeviceToHost, s->st));
+  HIP_TRY(hipMemcpyAsync(cnt, L.counters, sizeof(cnt), hipMemcpyDeviceToHost, s->st));
   HIP_TRY(hipStreamSynchronize(s->st));
   *state = cnt[CNT_L0_OK] ? TBG_L0_PASSED : TBG_L0_FAILED;
   return TBG_OK;

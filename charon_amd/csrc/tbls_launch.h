@@ -210,6 +210,17 @@ struct DevBatch {
   uint32_t n_sets;
   const uint32_t* duty_set;   // [n_duties] the duty's set
   int32_t* set_status;        // [n_sets + SET_TAIL] TBG_SS_* per set (outputs), then SET_BAD, SET_ANY
+  // aggregate, then verify the aggregate (TBG_OP_AGGREGATE_VERIFY, k_aggver.hip): the batch
+  // itself decodes and recombines as TBG_OP_AGGREGATE does (rlc_group = rlc_batch = 0: no
+  // check of the partials); the checks run on a second VIEW of it, aggver_view below, in
+  // which every duty is one candidate -- its affine aggregate, handed over in agg_aff.
+  // The view's shape and the arrays only it owns are kept here, so that a replayed prefix
+  // derives its view from its own fields.  All null / 0 for every other op.
+  G2A* agg_aff;               // [n_duties] the affine aggregates (written beside the compressed bytes)
+  int32_t* av_status;         // [n_duties] the view's partial_status
+  uint32_t* av_counters;      // [CNT_WORDS] the view's counters
+  const uint32_t* av_iota;    // [n_duties + 1] 0, 1, 2, ...: the view's duty_first and partial_duty
+  uint32_t av_group, av_chunk, av_batch;  // the view's rlc_group, rlc_chunk, rlc_batch
 };
 static_assert(offsetof(DevBatch, msm_r) == offsetof(DevBatch, rlc_batch) + 8, "l0_tail_partials fills rlc_batch's padding");
 // set_status's tail words: SET_BAD counts the partials left invalid or
@@ -449,6 +460,34 @@ TBG_HD bool participates(uint32_t op, int32_t st) {
                                        : (st == TBG_PS_NOT_VERIFIED);
 }
 
+// The check side of a TBG_OP_AGGREGATE_VERIFY batch: a TBG_OP_VERIFY batch of its own in
+// which duty d is the one candidate d -- the affine aggregate under the duty's group key
+// and message.  The aggregates are sums of points that passed the subgroup test and are
+// never the identity (TBG_DS_AGG_IDENTITY is decided in the recombination), so the view
+// runs no decode and no subgroup test: sgb = 0, hence the classic level 0 (bucket MSM) and
+// no by-message merge, which both need the subgroup test's digits.  It shares the batch's
+// messages, H(m) and RLC work arrays (sized by duties in submit_impl: the batch itself runs
+// no check) and owns partial_status and counters.  Derived from the batch's own fields
+// alone: a replayed prefix's view is the prefix's.
+inline DevBatch aggver_view(const DevBatch& B) {
+  DevBatch V = B;
+  V.op = TBG_OP_VERIFY;
+  V.n_partials = B.n_duties;
+  V.duty_first = V.partial_duty = B.av_iota;
+  V.sig_aff = B.agg_aff;
+  V.partial_status = B.av_status;
+  V.counters = B.av_counters;
+  V.rlc_group = B.av_group;
+  V.rlc_chunk = B.av_chunk;
+  V.rlc_batch = B.av_batch;
+  V.sgb = 0;
+  V.l0_msg_share = TBG_L0_MSG_NEVER;
+  V.agg_aff = nullptr;
+  return V;
+}
+// What a launch's check levels ran on: the view for TBG_OP_AGGREGATE_VERIFY, else the batch.
+inline DevBatch checked_batch(const DevBatch& B) { return B.op == TBG_OP_AGGREGATE_VERIFY ? aggver_view(B) : B; }
+
 // Debug aid: with TBG_DEBUG_SYNC=1 in the environment every launch is
 // followed by a stream synchronisation and a line on stderr (kernel, ms,
 // status), so a faulting or runaway kernel names itself.  Off by default.
@@ -539,6 +578,12 @@ void launch_rlc_partials_list(const DevBatch& B, const G1A* pk_aff, hipStream_t 
 void launch_lagrange(const DevBatch& B, hipStream_t st, bool spec = false);
 void launch_aggregate(const DevBatch& B, hipStream_t st, bool spec = false);
 void launch_aggregate_finish(const DevBatch& B, hipStream_t st, bool spec = false);
+// TBG_OP_AGGREGATE_VERIFY (k_aggver.hip; B the batch, V = aggver_view(B)): after the
+// recombination, the duties that combined become V's candidates (and V's counters and
+// level-0 bucket sizes are zeroed, as k_decode_sigs does at the head of a verify chain);
+// after V's checks, their verdicts go into B.duty_status and a failed duty's agg96 is zeroed
+void launch_aggver_candidates(const DevBatch& B, const DevBatch& V, hipStream_t st);
+void launch_aggver_status(const DevBatch& B, const DevBatch& V, hipStream_t st);
 void launch_sk_to_pk(const uint8_t* sk32, uint32_t n, uint8_t* pk48, hipStream_t st);
 void launch_sign(const uint8_t* sk32, const uint32_t* item_msg, uint32_t n, const G2A* h_aff, const int32_t* h_status,
                  uint8_t* sig96, hipStream_t st);

@@ -62,7 +62,8 @@ struct SubBatch {
     b.duty_first = duty_first.data();
     b.sigs = src.sigs ? src.sigs + 96ull * p0 : nullptr;
     b.identifiers = src.identifiers ? src.identifiers + p0 : nullptr;
-    b.pubkey_ids = src.pubkey_ids ? src.pubkey_ids + p0 : nullptr;
+    // (one id per partial; under TBG_OP_AGGREGATE_VERIFY one group key per duty)
+    b.pubkey_ids = src.pubkey_ids ? src.pubkey_ids + (src.op == TBG_OP_AGGREGATE_VERIFY ? d0 : p0) : nullptr;
     b.duty_threshold = src.duty_threshold ? src.duty_threshold + d0 : nullptr;
     if (src.op == TBG_OP_AGGREGATE) return;
     // Messages: a contiguous increasing run (one message per duty, the usual
@@ -105,7 +106,7 @@ struct SubBatch {
 // What the per-context validate() checks, for the parts the split relies on.
 int validate_split(const tbg_batch* b) {
   if (!b || b->n_duties == 0 || !b->duty_first) return TBG_E_INVALID_ARG;
-  if (b->op < TBG_OP_VERIFY || b->op > TBG_OP_VERIFY_AGGREGATE) return TBG_E_INVALID_ARG;
+  if (b->op < TBG_OP_VERIFY || b->op > TBG_OP_AGGREGATE_VERIFY) return TBG_E_INVALID_ARG;
   if (b->duty_first[0] != 0 || b->duty_first[b->n_duties] != b->n_partials) return TBG_E_INVALID_ARG;
   for (uint32_t d = 0; d < b->n_duties; ++d)
     if (b->duty_first[d + 1] < b->duty_first[d]) return TBG_E_INVALID_ARG;

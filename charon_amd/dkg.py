@@ -4,6 +4,8 @@
                            partial against its pubshare, threshold-aggregate per DV
   verify_deposit_aggregates dkg/dkg.go:408-421  the aggregate of each DV verifies
                            under the DV's own public key
+  agg_and_verify_deposit_data  both of the above; the aggregates are recombined
+                           and verified under the DV keys in one launch
   agg_lock_hash_sig        dkg/dkg.go:428-478   verify every lock-hash partial,
                            then AggregateSignatures / AggregatePublicKeys
                            (plain sums: the multi-signature of all shares)
@@ -112,6 +114,34 @@ def verify_deposit_aggregates(aggs, msgs, engine=None) -> None:
             raise DKGError(str(r))
         if not r:
             raise DKGError("invalid deposit data aggregated signature")
+
+
+def agg_and_verify_deposit_data(data, shares, msgs, engine=None) -> dict:
+    """agg_deposit_data_sigs followed by verify_deposit_aggregates (dkg.go:593,
+    then :408-421), without the second pass's decode of what the first has
+    just encoded.  The partials are verified against their pubshares by the
+    same launch as before (the reference aborts on the first bad partial:
+    the errors and their order are agg_deposit_data_sigs'); then ONE
+    OP_AGGREGATE_VERIFY launch over the verified partials recombines every
+    DV's aggregate and checks it under the DV key.  Same return value and the
+    same DKGError strings as the pair."""
+    e = tbls._engine(engine)
+    aggs = agg_deposit_data_sigs(data, shares, msgs, e)  # (raises on a bad partial)
+    dvs = list(aggs)
+    if not dvs:
+        return {}
+    duties = [{"partials": [tbls.PartialSignature(p.share_idx, tbls.Signature(bytes(p.signature)))
+                            for p in data[dv]],
+               "msg": bytes(msgs[dv]), "public_key": tbls.PublicKey(bytes(dv))} for dv in dvs]
+    out = {}
+    for dv, r in zip(dvs, tbls.aggregate_and_verify_batch(duties, e)):
+        if isinstance(r, Exception):
+            # (a DV key that does not decode fails the check as it does in verify_deposit_aggregates)
+            if str(r) == "invalid aggregated signature" or str(r).startswith("verify aggregate: public key"):
+                raise DKGError("invalid deposit data aggregated signature")
+            raise DKGError(str(r))
+        out[dv] = r.raw
+    return out
 
 
 def agg_lock_hash_sig(data, shares, lock_hash: bytes, engine=None):

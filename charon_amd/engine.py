@@ -21,9 +21,13 @@ PS_ERR_FLAGS, PS_ERR_FIELD, PS_ERR_CURVE, PS_ERR_SUBGROUP, PS_ERR_IDENTITY, PS_E
 DS_OK, DS_NOT_AGGREGATED = 0, 1
 DS_INSUFFICIENT, DS_INSUFFICIENT_VALID = -20, -21
 DS_AGG_TOO_FEW, DS_AGG_DUPLICATE_ID, DS_AGG_IDENTITY, DS_DECODE = -22, -23, -24, -25
+DS_AGG_INVALID, DS_AGG_PUBKEY = -26, -27  # OP_AGGREGATE_VERIFY: the aggregate's check / the duty's group key
 # per-set status (TBG_SS_*, submit_sets): ERROR < INVALID < VALID
 SS_ERROR, SS_INVALID, SS_VALID = 30, 31, 32
 OP_VERIFY, OP_AGGREGATE, OP_VERIFY_AGGREGATE = 1, 2, 3
+# aggregate every duty, then CoreVerify the aggregate under the duty's group key, in one
+# launch: pubkey_ids holds one resident id per DUTY
+OP_AGGREGATE_VERIFY = 4
 NO_PUBKEY = 0xFFFFFFFF
 TIMING_KEYS = ["decode", "hash", "combine", "h_lines", "verify", "lagrange", "aggregate", "total"]
 VERIFY_RLC, VERIFY_EACH = 0, 1
@@ -171,6 +175,11 @@ class Engine:
             data, off = _u8(data), _u32(off)
             duty_msg = _u32(duty_msg)
             pubkey_ids = _u32(pubkey_ids)
+            # one id per partial; under OP_AGGREGATE_VERIFY one group key per DUTY (the library
+            # has no length to check it against)
+            if op == OP_AGGREGATE_VERIFY and pubkey_ids.shape != (nd,):
+                raise ValueError(f"pubkey_ids: OP_AGGREGATE_VERIFY takes one id per duty ({nd}), got "
+                                 f"{pubkey_ids.size}")
             keep += [data, off, duty_msg, pubkey_ids]
             b.n_msgs = len(off) - 1
             b.msgs, b.msg_off, b.duty_msg, b.pubkey_ids = _ptr(data), _ptr(off), _ptr(duty_msg), _ptr(pubkey_ids)

@@ -14,6 +14,8 @@
   Aggregator                 core/sigagg/sigagg.go:40-103
     .aggregate_batch         every DV that reached threshold in one store call,
                              aggregated in one GPU launch
+    .aggregate_verified_batch  the same, each aggregate verified under its DV's
+                             group key in that launch
 
 Data model: a partial is ``ParSignedData`` -- the eth2 signed object reduced to
 what the verify / aggregate path reads (domain name, epoch, 32-byte message
@@ -306,6 +308,19 @@ class MemDB:
 
 
 # --------------------------------------------------------------------- sigagg
+def _group_key(pubkey):
+    """A DV's group key as tbls.PublicKey: core.PubKey is the 0x-prefixed hex of
+    the 48 bytes; the bytes themselves and tbls.PublicKey pass through."""
+    if pubkey is None or isinstance(pubkey, tbls.PublicKey):
+        return pubkey
+    if isinstance(pubkey, str):
+        try:
+            pubkey = bytes.fromhex(pubkey[2:] if pubkey.startswith("0x") else pubkey)
+        except ValueError:
+            raise ParSigError("decode public key hex") from None
+    return tbls.PublicKey(bytes(pubkey))
+
+
 class Aggregator:
     """sigagg.Aggregator: threshold partials -> aggregate signed data."""
 
@@ -342,6 +357,58 @@ class Aggregator:
             duties.append([tbls.PartialSignature(p.share_idx, tbls.Signature(bytes(p.signature))) for p in parsigs])
         if duties:
             for k, r in zip(live, tbls.aggregate_batch(duties, self.engine)):
+                if isinstance(r, Exception):
+                    msg = str(r)
+                    out[k] = ParSigError("convert signature: " + msg if msg.startswith("uncompress") else msg)
+                else:
+                    out[k] = items[k][2][0].set_signature(r.raw)
+        for (duty, pubkey, _), r in zip(items, out):
+            if not isinstance(r, Exception):
+                for sub in self.subs:
+                    sub(duty, pubkey, r)
+        return out
+
+    def aggregate_verified_batch(self, items, spec: signing.Spec):
+        """aggregate_batch, and every aggregate verified under its DV's group
+        public key before anyone sees it -- what the reference's tests assert
+        of every Aggregator output (tbls.Verify(groupPK, ...)), in the same
+        GPU launch as the recombination (tbls.aggregate_and_verify_batch).
+        items: [(duty, pubkey, [ParSignedData])], pubkey the DV's group key
+        (core.PubKey hex, its 48 bytes, or tbls.PublicKey).  The message is the signing root of
+        the item's first partial (domain, epoch, message root), formed as
+        signing.verify_batch forms it.  Returns per item the aggregate
+        ParSignedData or a ParSigError -- aggregate_batch's, a signing error,
+        or "invalid aggregated signature"; subscribers are called only for
+        verified aggregates."""
+        items = list(items)
+        out = [None] * len(items)
+        live = []
+        for k, (duty, pubkey, parsigs) in enumerate(items):
+            err = self._check(parsigs)
+            if err is None:
+                p = parsigs[0]
+                try:
+                    spec.domain(p.domain, p.epoch)
+                    if len(p.message_root) != 32:
+                        raise signing.SigningError("marshal signing data")
+                    _group_key(pubkey)
+                except (signing.SigningError, ParSigError, tbls.TblsError) as e:
+                    err = ParSigError(str(e))
+            if err is not None:
+                out[k] = err
+                continue
+            live.append(k)
+        if live:
+            firsts = [items[k][2][0] for k in live]
+            roots = signing.get_data_roots(spec, [p.domain for p in firsts], [p.epoch for p in firsts],
+                                           [p.message_root for p in firsts])
+            duties = []
+            for k, root in zip(live, roots):
+                _, pubkey, parsigs = items[k]
+                pk = _group_key(pubkey)
+                duties.append({"partials": [tbls.PartialSignature(p.share_idx, tbls.Signature(bytes(p.signature)))
+                                            for p in parsigs], "msg": root, "public_key": pk})
+            for k, r in zip(live, tbls.aggregate_and_verify_batch(duties, self.engine)):
                 if isinstance(r, Exception):
                     msg = str(r)
                     out[k] = ParSigError("convert signature: " + msg if msg.startswith("uncompress") else msg)

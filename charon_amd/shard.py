@@ -61,15 +61,17 @@ class SubBatch:
 
 
 def sub_batch(d0, d1, duty_first, sigs, identifiers, pubkey_ids=None, duty_threshold=None, msg_data=None,
-              msg_off=None, duty_msg=None) -> SubBatch:
+              msg_off=None, duty_msg=None, key_per_duty: bool = False) -> SubBatch:
     """Slice duties [d0, d1): partial arrays by offset, duty_first rebased,
-    and the messages the range uses re-indexed in order of first use."""
+    and the messages the range uses re-indexed in order of first use.
+    key_per_duty: pubkey_ids holds one id per duty (OP_AGGREGATE_VERIFY's
+    group keys) and is cut at the duty offsets, as tbls_multi.hip does."""
     duty_first = np.asarray(duty_first, dtype=np.int64)
     p0, p1 = int(duty_first[d0]), int(duty_first[d1])
     sb = SubBatch(d0, d1, p0, p1, (duty_first[d0:d1 + 1] - p0).astype(np.uint32), np.asarray(sigs)[p0:p1],
                   np.asarray(identifiers)[p0:p1], None, None, None, None, None)
     if pubkey_ids is not None:
-        sb.pubkey_ids = np.asarray(pubkey_ids)[p0:p1]
+        sb.pubkey_ids = np.asarray(pubkey_ids)[d0:d1] if key_per_duty else np.asarray(pubkey_ids)[p0:p1]
     if duty_threshold is not None:
         sb.duty_threshold = np.asarray(duty_threshold)[d0:d1]
     if duty_msg is not None:

@@ -16,6 +16,7 @@ plus the batch entry points the batch-aware call sites use:
   verify_batch(items) -> list[bool | TblsError]
   verify_and_aggregate_batch(duties) -> list[(Signature, signers) | TblsError]
   aggregate_batch(duties) -> list[Signature | TblsError]
+  aggregate_and_verify_batch(duties) -> list[Signature | TblsError]
 
 Keys and signatures are carried as their wire encodings (48-byte G1 /
 96-byte G2, ZCash-compressed); decoding, hashing, pairing and Lagrange
@@ -315,7 +316,58 @@ def aggregate_batch(duties, engine=None):
     return out
 
 
+def aggregate_and_verify_batch(duties, engine=None):
+    """duties: iterable of dicts {partials, msg, public_key}.  Per duty:
+    tbls.Aggregate over all its partials, then tbls.Verify of the aggregate
+    under the duty's group public key -- in ONE launch (OP_AGGREGATE_VERIFY:
+    the aggregate is checked in the form the recombination leaves it in, with
+    no second decode).  Returns the aggregate Signature, or a TblsError: the
+    strings of aggregate_batch when the combination fails, "invalid aggregated
+    signature" when the aggregate does not verify, "verify aggregate: public
+    key ..." when the duty's key is missing or does not decode.  Equal
+    messages are hashed once; group keys stay resident like pubshares."""
+    duties = list(duties)
+    if not duties:
+        return []
+    e = _engine(engine)
+    duty_first, sigs, ids, _, _, _ = _duty_arrays(duties, False)
+    keys = [_raw(d["public_key"], PublicKey) if d.get("public_key") is not None else None for d in duties]
+    present = [k for k in keys if k is not None]
+    it = iter(_pk_cache.ids_for(e, present))
+    pk_ids = [next(it) if k is not None else eng.NO_PUBKEY for k in keys]
+    msgs, duty_msg = _distinct_msgs([bytes(d["msg"]) for d in duties])
+    res = e.run(eng.OP_AGGREGATE_VERIFY, duty_first, sigs, ids, msgs=msgs, duty_msg=duty_msg, pubkey_ids=pk_ids)
+    out = []
+    for d, ds in enumerate(res.duty_status.tolist()):
+        if ds == eng.DS_OK:
+            out.append(Signature(bytes(res.agg[d])))
+        elif ds == eng.DS_AGG_INVALID:
+            out.append(TblsError("invalid aggregated signature"))
+        elif ds == eng.DS_AGG_PUBKEY:
+            if keys[d] is None:
+                why = "cannot be nil"
+            else:
+                st = _pk_cache.statuses_for(e, [keys[d]])[0]
+                why = _PK_ERRORS.get(st, f"status {st}")
+                why = why[len("public key "):] if why.startswith("public key ") else why
+            out.append(TblsError("verify aggregate: public key " + why))
+        else:
+            out.append(TblsError(_DUTY_ERRORS.get(ds, f"aggregate signatures: status {ds}")))
+    return out
+
+
 # ------------------------------------------------------------ Go-API mirror
+def aggregate_and_verify(partial_sigs, msg: bytes, public_key, engine=None) -> Signature:
+    """tbls.Aggregate, then tbls.Verify of the result under the group key (what
+    the DKG and the sigagg tests do with two calls), in one launch.  Raises the
+    TblsError of aggregate_and_verify_batch."""
+    r = aggregate_and_verify_batch([{"partials": list(partial_sigs), "msg": msg, "public_key": public_key}],
+                                   engine)[0]
+    if isinstance(r, Exception):
+        raise r
+    return r
+
+
 def verify(pk, msg: bytes, sig, engine=None) -> bool:
     """tbls.Verify: (bool, error).  Decode failures raise TblsError."""
     if pk is None:

@@ -57,6 +57,10 @@ extern "C" {
 #define TBG_DS_AGG_DUPLICATE_ID (-23)    /* CombineSignatures: identifiers collide            */
 #define TBG_DS_AGG_IDENTITY (-24)        /* CombineSignatures: identity input or result       */
 #define TBG_DS_DECODE (-25)              /* a partial failed to decode (SigFromCore error)    */
+#define TBG_DS_AGG_INVALID (-26)          /* TBG_OP_AGGREGATE_VERIFY: the aggregate fails CoreVerify
+                                          * under the duty's key (or its H(m) is unusable)     */
+#define TBG_DS_AGG_PUBKEY (-27)           /* TBG_OP_AGGREGATE_VERIFY: the duty's key id is TBG_NO_PUBKEY
+                                          * or unknown, or the key failed to decode / is the identity */
 #define TBG_DS_NOT_AGGREGATED 1          /* TBG_OP_VERIFY: no aggregate produced              */
 
 /* ---- per-set status (int32, tbg_submit_sets) ------------------------------
@@ -71,7 +75,20 @@ extern "C" {
 typedef enum {
   TBG_OP_VERIFY = 1,           /* per partial: CoreVerify(pk, msg(duty), sig)                 */
   TBG_OP_AGGREGATE = 2,        /* per duty: CombineSignatures(all partials), no verification  */
-  TBG_OP_VERIFY_AGGREGATE = 3  /* per duty: VerifyAndAggregate(tss, partials, msg)            */
+  TBG_OP_VERIFY_AGGREGATE = 3, /* per duty: VerifyAndAggregate(tss, partials, msg)            */
+  /* per duty: CombineSignatures(all partials) as TBG_OP_AGGREGATE does it, then
+   * CoreVerify(pk(duty), msg(duty), aggregate) in the same launch (the aggregate is handed
+   * over in affine form: no re-decode, no second subgroup test).  pubkey_ids holds ONE
+   * resident id per DUTY (the group key); msgs / msg_off / duty_msg are required;
+   * duty_threshold is ignored.  partial_status as under TBG_OP_AGGREGATE.  duty_status: the
+   * codes of TBG_OP_AGGREGATE when the combination fails; TBG_DS_OK when the aggregate
+   * verifies; TBG_DS_AGG_INVALID; TBG_DS_AGG_PUBKEY.  agg96[d] holds the aggregate only
+   * under TBG_DS_OK and is all zero otherwise, as for a failed combination.  Equal, for every
+   * input and schedule, to TBG_OP_AGGREGATE followed by TBG_OP_VERIFY of (pk(d), msg(d),
+   * agg(d)) over the duties that came out TBG_DS_OK.  tbg_fetch_stats / _fallback / _level0 /
+   * _shape describe the aggregate check (one candidate per duty; level 0 by the bucket
+   * MSM), tbg_fetch_subgroup* the partials' decode.  tbg_submit_sets refuses it. */
+  TBG_OP_AGGREGATE_VERIFY = 4
 } tbg_op;
 
 typedef struct tbg_ctx tbg_ctx;
@@ -220,14 +237,15 @@ typedef struct {
   uint32_t n_duties;
   uint32_t n_partials;
   uint32_t n_msgs;
-  const uint8_t* msgs;             /* concatenated message bytes (VERIFY*)            */
+  const uint8_t* msgs;             /* concatenated message bytes (VERIFY*, AGGREGATE_VERIFY) */
   const uint32_t* msg_off;         /* [n_msgs + 1]                                    */
-  const uint32_t* duty_msg;        /* [n_duties]     (VERIFY*)                        */
+  const uint32_t* duty_msg;        /* [n_duties]     (VERIFY*, AGGREGATE_VERIFY)      */
   const uint32_t* duty_first;      /* [n_duties + 1]                                  */
   const uint32_t* duty_threshold;  /* [n_duties]     (VERIFY_AGGREGATE)               */
   const uint8_t* sigs;             /* [n_partials * 96] ZCash-compressed G2           */
   const uint8_t* identifiers;      /* [n_partials] share index (Lagrange x)           */
-  const uint32_t* pubkey_ids;      /* [n_partials] resident pubkey id (VERIFY*)       */
+  const uint32_t* pubkey_ids;      /* [n_partials] resident pubkey id (VERIFY*);
+                                    * [n_duties] the duty's group key (AGGREGATE_VERIFY) */
 } tbg_batch;
 
 int tbg_init(const tbg_config* cfg, tbg_ctx** out);
@@ -253,7 +271,8 @@ uint32_t tbg_pubkey_count(const tbg_ctx* ctx);
 int tbg_submit(tbg_ctx* ctx, const tbg_batch* batch, tbg_ticket* ticket);
 
 /* Enqueue several batches (same op) as ONE device batch: they are packed
- * back to back (indices rebased) and every kernel of the chain runs once
+ * back to back (indices rebased; the per-duty key ids of TBG_OP_AGGREGATE_VERIFY
+ * by duty count) and every kernel of the chain runs once
  * over all of them, so concurrent callers' batches fill the GPU together
  * instead of queueing small launches on separate streams (the call site
  * coalesces what arrives within its window -- parsigex peers, validatorapi
@@ -283,7 +302,8 @@ int tbg_collect(tbg_ctx* ctx, tbg_ticket ticket, int32_t* partial_status, int32_
  * duties), and an unconfigured G shrinks (16 -> 8 -> 4) while the padding
  * would pass 1/8 of the duties.  A false accept stays <= 2^-64 per check.
  * TBG_E_INVALID_ARG unless set_first[0] == 0, set_first is non-decreasing,
- * set_first[n_sets] == n_duties and op == TBG_OP_VERIFY.
+ * set_first[n_sets] == n_duties and op == TBG_OP_VERIFY (TBG_OP_AGGREGATE_VERIFY
+ * included: no set launch aggregates).
  * partial_status (optional): negative codes exact; a candidate is
  * TBG_PS_VALID if its set is TBG_SS_VALID, else TBG_PS_NOT_VERIFIED.
  * A set ticket works with tbg_poll, tbg_replay, tbg_replay_profile,
@@ -425,7 +445,10 @@ int tbg_sign(tbg_ctx* ctx, const uint8_t* sk32, uint32_t n, const uint8_t* msgs,
 
 /* Last kernel timings of the context (milliseconds, HIP events on the
  * engine's streams): [decode, hash, combine (RLC sums + group lines),
- * H lines, verify (all check levels), lagrange, aggregate, total]. */
+ * H lines, verify (all check levels), lagrange, aggregate, total]; ms8 has
+ * exactly 8 entries (NULL: TBG_E_INVALID_ARG).  Under TBG_OP_AGGREGATE_VERIFY
+ * "verify" is the aggregates' checks, "lagrange" / "aggregate" the
+ * recombination (which runs before them) and "combine" the checks' key side. */
 int tbg_last_timings(const tbg_ctx* ctx, float* ms8);
 
 /* ---- one process, several GPUs (BASELINE config 4) -----------------------
