@@ -1862,6 +1862,175 @@ int tbg_sign(tbg_ctx* c, const uint8_t* sk32, uint32_t n, const uint8_t* msgs, c
   return rc;
 }
 
+}  // extern "C"
+
+// ---- the hardened signer (k_keyed.hip, bls_ctmul.h) ------------------------
+namespace {
+
+// TBG_KS_* of a 32-byte big-endian key: zero, or a word-wise compare against
+// r -- every word is read and subtracted whatever the earlier ones were.
+int32_t keyed_status(const uint8_t* b) {
+  static const uint32_t R_W[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u,
+                                  0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};  // r, little-endian words
+  uint32_t nz = 0;
+  uint64_t borrow = 0;
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t w = ((uint32_t)b[31 - 4 * i]) | ((uint32_t)b[30 - 4 * i] << 8) | ((uint32_t)b[29 - 4 * i] << 16) |
+                       ((uint32_t)b[28 - 4 * i] << 24);
+    nz |= w;
+    borrow = (((uint64_t)w - R_W[i] - borrow) >> 63) & 1u;
+  }
+  const int32_t ge = (int32_t)borrow - 1;                      // all ones: sk >= r (no final borrow)
+  const int32_t zero = (int32_t)((nz | (0u - nz)) >> 31) - 1;  // all ones: sk == 0
+  return (TBG_KS_ZERO & zero) | (TBG_KS_RANGE & ge & ~zero);
+}
+
+void keyed_wipe(void* p, size_t n) {
+  volatile uint8_t* v = (volatile uint8_t*)p;
+  for (size_t i = 0; i < n; ++i) v[i] = 0;
+}
+
+// Everything of one hardened call that held key bytes: the device copy of the
+// keys (inside the call's workspace) and the pinned staging they were
+// uploaded from.  Whatever way the call ends, the device bytes are zeroed ON
+// THE STREAM (behind the kernels that read them), the stream is drained, the
+// staging is zeroed, and only then is either released.
+struct KeyedScope {
+  hipStream_t st = nullptr;
+  uint8_t* d_base = nullptr;  // the workspace (hipMalloc)
+  uint8_t* d_sk = nullptr;    // [sk_bytes] inside it
+  uint8_t* h_sk = nullptr;    // [sk_bytes] pinned (hipHostMalloc)
+  size_t sk_bytes = 0;
+  size_t o = 0;
+  ~KeyedScope() {
+    if (d_sk) (void)hipMemsetAsync(d_sk, 0, sk_bytes, st);
+    (void)hipStreamSynchronize(st);
+    if (h_sk) {
+      keyed_wipe(h_sk, sk_bytes);
+      (void)hipHostFree(h_sk);
+    }
+    if (d_base) (void)hipFree(d_base);
+  }
+  uint8_t* sec(size_t bytes) {
+    uint8_t* p = d_base + o;
+    o += align_up(bytes, 16);
+    return p;
+  }
+  // The workspace and the staging; the keys go into the staging with every
+  // rejected one replaced by 1 (masks, no branch on a key byte), their codes into kst.
+  int open(hipStream_t stream, size_t work_bytes, const uint8_t* sk32, uint32_t n, std::vector<int32_t>& kst) {
+    st = stream;
+    sk_bytes = 32ull * n;
+    if (hipMalloc(&d_base, work_bytes) != hipSuccess) { d_base = nullptr; return TBG_E_OOM; }
+    if (hipHostMalloc((void**)&h_sk, sk_bytes, hipHostMallocDefault) != hipSuccess) { h_sk = nullptr; return TBG_E_OOM; }
+    kst.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      const uint8_t* k = sk32 + 32ull * i;
+      kst[i] = keyed_status(k);
+      const uint8_t keep = (uint8_t)(((uint32_t)kst[i] | (0u - (uint32_t)kst[i])) >> 31) - 1;  // 0xff: accepted
+      for (int j = 0; j < 32; ++j) h_sk[32ull * i + j] = (uint8_t)((k[j] & keep) | ((j == 31 ? 1 : 0) & ~keep));
+    }
+    d_sk = sec(sk_bytes);
+    return hipMemcpyAsync(d_sk, h_sk, sk_bytes, hipMemcpyHostToDevice, st) == hipSuccess ? TBG_OK : TBG_E_DEVICE;
+  }
+};
+
+// the rejected keys' outputs and codes (their lanes ran on the key 1)
+void keyed_mask(const std::vector<int32_t>& kst, uint8_t* out, size_t width, int32_t* status) {
+  for (size_t i = 0; i < kst.size(); ++i) {
+    if (kst[i] == TBG_KS_OK) continue;
+    memset(out + width * i, 0, width);
+    status[i] = kst[i];
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int tbg_sk_to_pk_ct(tbg_ctx* c, const uint8_t* sk32, uint32_t n, uint8_t* pk48, int32_t* status) {
+  if (!c || (n && (!sk32 || !pk48 || !status))) return TBG_E_INVALID_ARG;
+  if (n == 0) return TBG_OK;
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t tab_bytes = 4 * ct_tab_words_g1();
+  std::vector<int32_t> kst;
+  KeyedScope ks;
+  int rc = ks.open(c->stream, align_up(32ull * n, 16) + align_up(tab_bytes, 16) + align_up(48ull * n, 16) +
+                                  align_up(4ull * n, 16), sk32, n, kst);
+  if (rc != TBG_OK) return rc;
+  hipStream_t st = c->stream;
+  uint32_t* d_tab = (uint32_t*)ks.sec(tab_bytes);
+  uint8_t* d_pk = ks.sec(48ull * n);
+  int32_t* d_st = (int32_t*)ks.sec(4ull * n);
+  launch_ct_table_g1(d_tab, st);
+  launch_sk_to_pk_ct(ks.d_sk, n, d_tab, d_pk, d_st, st);
+  if (hipGetLastError() != hipSuccess) rc = TBG_E_DEVICE;
+  if (rc == TBG_OK && (hipMemcpyAsync(pk48, d_pk, 48ull * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                       hipMemcpyAsync(status, d_st, 4ull * n, hipMemcpyDeviceToHost, st) != hipSuccess))
+    rc = TBG_E_DEVICE;
+  if (hipStreamSynchronize(st) != hipSuccess) rc = TBG_E_DEVICE;
+  if (rc == TBG_OK) keyed_mask(kst, pk48, 48, status);
+  return rc;
+}
+
+int tbg_sign_ct(tbg_ctx* c, const uint8_t* sk32, uint32_t n, const uint8_t* msgs, const uint32_t* msg_off, uint32_t n_msgs,
+                const uint32_t* item_msg, uint8_t* sig96, int32_t* status) {
+  if (!c || (n && (!sk32 || !sig96 || !item_msg || !status)) || n_msgs == 0 || !msg_off) return TBG_E_INVALID_ARG;
+  if (msg_off[0] != 0) return TBG_E_INVALID_ARG;
+  for (uint32_t m = 0; m < n_msgs; ++m)
+    if (msg_off[m + 1] < msg_off[m]) return TBG_E_INVALID_ARG;
+  for (uint32_t i = 0; i < n; ++i)
+    if (item_msg[i] >= n_msgs) return TBG_E_INVALID_ARG;
+  if (n == 0) return TBG_OK;
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t mb = msg_off[n_msgs];
+  const size_t tab_bytes = 4 * ct_tab_words_g2(n_msgs);
+  const size_t need = align_up(32ull * n, 16) + align_up(mb + 1, 16) + align_up(4ull * (n_msgs + 1), 16) +
+                      align_up(4ull * n, 16) + align_up(sizeof(G2A) * (size_t)n_msgs, 16) + align_up(4ull * n_msgs, 16) +
+                      align_up(96ull * n, 16) + align_up(3 * sizeof(G2J) * (size_t)n_msgs, 16) + align_up(tab_bytes, 16) +
+                      align_up(4ull * n, 16);
+  std::vector<int32_t> kst;
+  KeyedScope ks;
+  int rc = ks.open(c->stream, need, sk32, n, kst);
+  if (rc != TBG_OK) return rc;
+  hipStream_t st = c->stream;
+  uint8_t* d_msgs = ks.sec(mb + 1);
+  uint32_t* d_off = (uint32_t*)ks.sec(4ull * (n_msgs + 1));
+  uint32_t* d_im = (uint32_t*)ks.sec(4ull * n);
+  G2A* d_h = (G2A*)ks.sec(sizeof(G2A) * (size_t)n_msgs);
+  int32_t* d_hs = (int32_t*)ks.sec(4ull * n_msgs);
+  uint8_t* d_sig = ks.sec(96ull * n);
+  G2J* d_hj = (G2J*)ks.sec(3 * sizeof(G2J) * (size_t)n_msgs);
+  uint32_t* d_tab = (uint32_t*)ks.sec(tab_bytes);
+  int32_t* d_st = (int32_t*)ks.sec(4ull * n);
+  if ((mb && hipMemcpyAsync(d_msgs, msgs, mb, hipMemcpyHostToDevice, st) != hipSuccess) ||
+      hipMemcpyAsync(d_off, msg_off, 4ull * (n_msgs + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(d_im, item_msg, 4ull * n, hipMemcpyHostToDevice, st) != hipSuccess)
+    rc = TBG_E_DEVICE;
+  if (rc == TBG_OK) {
+    DevBatch B{};
+    memset(&B, 0, sizeof(B));
+    B.n_msgs = n_msgs;
+    B.msgs = d_msgs;
+    B.msg_off = d_off;
+    B.h_aff = d_h;
+    B.h_status = d_hs;
+    B.h_jac = d_hj;
+    launch_hash_msgs(B, st);
+    launch_ct_table_g2(d_h, d_hs, n_msgs, d_tab, st);
+    launch_sign_ct(ks.d_sk, d_im, n, n_msgs, d_tab, d_hs, d_sig, d_st, st);
+    if (hipGetLastError() != hipSuccess) rc = TBG_E_DEVICE;
+  }
+  if (rc == TBG_OK && (hipMemcpyAsync(sig96, d_sig, 96ull * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                       hipMemcpyAsync(status, d_st, 4ull * n, hipMemcpyDeviceToHost, st) != hipSuccess))
+    rc = TBG_E_DEVICE;
+  if (hipStreamSynchronize(st) != hipSuccess) rc = TBG_E_DEVICE;
+  if (rc == TBG_OK) keyed_mask(kst, sig96, 96, status);
+  return rc;
+}
+
 // ---- plain sums and FastAggregateVerify (k_sum.hip) -----------------------
 // dkg/dkg.go:466-476 (AggregateSignatures / AggregatePublicKeys of the lock
 // hash), cluster/lock.go:155-177 (FastAggregateVerify over every pubshare).

@@ -587,5 +587,16 @@ void launch_aggver_status(const DevBatch& B, const DevBatch& V, hipStream_t st);
 void launch_sk_to_pk(const uint8_t* sk32, uint32_t n, uint8_t* pk48, hipStream_t st);
 void launch_sign(const uint8_t* sk32, const uint32_t* item_msg, uint32_t n, const G2A* h_aff, const int32_t* h_status,
                  uint8_t* sig96, hipStream_t st);
+// the hardened signer (k_keyed.hip, bls_ctmul.h): the tables of the multiples 0..8 of the
+// public base points -- the G1 generator (one table), H(m) of every message -- then the
+// fixed-schedule products.  ct_tab_words: 32-bit words of such a table set.
+size_t ct_tab_words_g1();
+size_t ct_tab_words_g2(uint32_t n_msgs);
+void launch_ct_table_g1(uint32_t* tab, hipStream_t st);
+void launch_ct_table_g2(const G2A* h_aff, const int32_t* h_status, uint32_t n_msgs, uint32_t* tab, hipStream_t st);
+void launch_sk_to_pk_ct(const uint8_t* sk32, uint32_t n, const uint32_t* tab, uint8_t* pk48, int32_t* status,
+                        hipStream_t st);
+void launch_sign_ct(const uint8_t* sk32, const uint32_t* item_msg, uint32_t n, uint32_t n_msgs, const uint32_t* tab,
+                    const int32_t* h_status, uint8_t* sig96, int32_t* status, hipStream_t st);
 
 }  // namespace tbg

@@ -15,6 +15,13 @@
                            signature: FastAggregateVerify over every pubshare,
                            over the hash the caller recomputed (not the JSON's)
 
+and the producing halves, through the hardened signer (tbg_sign_ct):
+
+  sign_deposit_data        dkg/dkg.go:505-542   a peer's deposit-data partials
+  sign_lock_hash           dkg/dkg.go:480-503   a peer's lock-hash partials
+  create_cluster_sign_deposit_data  cmd/createcluster.go:185-207
+  agg_sign_lock_hash       cmd/createcluster.go:487-515  sign with every share, sum
+
 Each step is one GPU submit over the whole ceremony (every DV and peer at
 once) instead of the reference's per-partial loop: the deposit data runs as a
 TBG_OP_VERIFY_AGGREGATE batch with threshold = the partial count (all must
@@ -187,7 +194,76 @@ def verify_multi_signature(agg_pk48: bytes, msg: bytes, agg_sig96: bytes, engine
     return r
 
 
-def create_cluster_tss(secrets, t: int, n: int, rng, engine=None):
+# ---- the producing halves: every signature a ceremony makes, through the
+# hardened signer (tbls.sign_batch: tbg_sign_ct, fixed-schedule [sk]H(m), key
+# material wiped) -- each one launch over every share at hand.
+def _share_value(s) -> int:
+    return s.value if isinstance(s, tbls.SecretKeyShare) else int(s)
+
+
+def _sign_all(secrets, msgs, engine):
+    """One hardened launch; the first failing item (caller's order) raises."""
+    out = []
+    for r in tbls.sign_batch(zip(secrets, msgs), engine):
+        if isinstance(r, Exception):
+            raise DKGError(str(r))
+        out.append(r.raw)
+    return out
+
+
+def sign_deposit_data(shares, share_idx: int, msgs, engine=None) -> dict:
+    """signDepositData (dkg/dkg.go:505-542): this peer's partial signature of
+    every DV's deposit-data signing root.  shares {dv_pk48: secret share (int
+    or SecretKeyShare)}, share_idx this peer's 1-based index, msgs {dv_pk48:
+    signing root} (the roots are host work: deposit.GetMessageSigningRoot).
+    Returns {dv_pk48: DKGPartial}.  A zero or out-of-range share raises
+    DKGError("unmarshal secret: ...") (tblsconv.ShareToSecret)."""
+    dvs = list(shares)
+    for dv in dvs:
+        if dv not in msgs:
+            raise DKGError("deposit data signing root missing for a distributed validator")
+    sigs = _sign_all([_share_value(shares[dv]) for dv in dvs], [bytes(msgs[dv]) for dv in dvs], engine)
+    return {dv: DKGPartial(share_idx, sig) for dv, sig in zip(dvs, sigs)}
+
+
+def sign_lock_hash(shares, share_idx: int, lock_hash: bytes, engine=None) -> dict:
+    """signLockHash (dkg/dkg.go:480-503): this peer's partial signature of the
+    lock hash with every share it holds -- one message, hashed once.
+    Arguments and errors as sign_deposit_data.  Returns {dv_pk48: DKGPartial}."""
+    dvs = list(shares)
+    sigs = _sign_all([_share_value(shares[dv]) for dv in dvs], [bytes(lock_hash)] * len(dvs), engine)
+    return {dv: DKGPartial(share_idx, sig) for dv, sig in zip(dvs, sigs)}
+
+
+def create_cluster_sign_deposit_data(secrets, msgs, engine=None) -> list:
+    """signDepositDatas of `charon create cluster` (cmd/createcluster.go:185-207):
+    every validator SECRET signs its own deposit-data signing root.  secrets
+    and msgs are parallel lists (the roots depend on the public keys, which
+    tbls.secret_to_public_key_batch gives in one launch).  Returns the 96-byte
+    signatures in the same order."""
+    secrets, msgs = list(secrets), [bytes(m) for m in msgs]
+    if len(secrets) != len(msgs):
+        raise DKGError("one deposit data signing root per validator secret is needed")
+    return _sign_all(secrets, msgs, engine)
+
+
+def agg_sign_lock_hash(share_lists, lock_hash: bytes, engine=None) -> bytes:
+    """aggSign (cmd/createcluster.go:487-515): the lock hash signed with every
+    share of every validator (one hardened launch), then AggregateSignatures
+    (the existing plain sum).  share_lists: one list of shares per validator.
+    Returns the 96-byte aggregate."""
+    flat = [_share_value(s) for shares in share_lists for s in shares]
+    if not flat:
+        raise DKGError("aggregate signatures: no signatures")
+    e = tbls._engine(engine)
+    sigs = _sign_all(flat, [bytes(lock_hash)] * len(flat), e)
+    agg, st, _ = e.sum_sigs(b"".join(sigs), [0, len(sigs)])
+    if int(st[0]) != eng.DS_OK:
+        raise DKGError("aggregate signatures: " + tbls._DUTY_ERRORS.get(int(st[0]), str(int(st[0]))))
+    return bytes(agg[0])
+
+
+def create_cluster_tss(secrets, t: int, n: int, rng, engine=None, hardened=False):
     """getTSSShares of `charon create cluster` (cmd/createcluster.go:250-270):
     every validator secret split t-of-n and its TSS.  One split on the host
     (integers), ONE sk_to_pk launch for every commitment and every pubshare
@@ -196,7 +272,10 @@ def create_cluster_tss(secrets, t: int, n: int, rng, engine=None):
     resident for the verifies that follow, instead of a SplitSecret + NewTSS
     pair per validator.  Returns (list of TSS, list of share lists).  Host
     integers and the test-only tbg_sk_to_pk: not side-channel safe, not for
-    production keys (tbls.split_secret)."""
+    production keys (tbls.split_secret).  hardened=True forms every commitment
+    and pubshare on the fixed schedule (tbg_sk_to_pk_ct; a zero or out-of-range
+    scalar raises); the split itself stays on host integers and keeps the
+    warning -- the product's caller is Go, which splits in kryptology."""
     e = tbls._engine(engine)
     splits, polys = [], []
     for s in secrets:
@@ -206,7 +285,7 @@ def create_cluster_tss(secrets, t: int, n: int, rng, engine=None):
     if not splits:
         return [], []
     scalars = [c for p in polys for c in p] + [s.value for sh in splits for s in sh]
-    pks = [bytes(k) for k in e.sk_to_pk(b"".join(tbls._sk32(v) for v in scalars))]
+    pks = tbls._sk_to_pk(scalars, e, hardened, "unmarshal secret")
     nd = len(polys)
     commits, shares48 = pks[:nd * t], pks[nd * t:]
     keys = tbls.key_from_bytes_batch(shares48, e)

@@ -24,6 +24,8 @@ DS_AGG_TOO_FEW, DS_AGG_DUPLICATE_ID, DS_AGG_IDENTITY, DS_DECODE = -22, -23, -24,
 DS_AGG_INVALID, DS_AGG_PUBKEY = -26, -27  # OP_AGGREGATE_VERIFY: the aggregate's check / the duty's group key
 # per-set status (TBG_SS_*, submit_sets): ERROR < INVALID < VALID
 SS_ERROR, SS_INVALID, SS_VALID = 30, 31, 32
+# per-item status of the hardened signer (TBG_KS_*, sk_to_pk_ct / sign_ct)
+KS_OK, KS_ZERO, KS_RANGE, KS_MSG = 0, -40, -41, -42
 OP_VERIFY, OP_AGGREGATE, OP_VERIFY_AGGREGATE = 1, 2, 3
 # aggregate every duty, then CoreVerify the aggregate under the duty's group key, in one
 # launch: pubkey_ids holds one resident id per DUTY
@@ -389,6 +391,28 @@ class Engine:
         self._check(self._lib.tbg_sign(self._h, _ptr(a), a.shape[0], _ptr(data), _ptr(off), len(off) - 1, _ptr(im),
                                        _ptr(out)), "tbg_sign")
         return out
+
+    # ------------------------------------------------------------ the hardened signer
+    def sk_to_pk_ct(self, sk32):
+        """SecretKey.GetPublicKey on the fixed schedule (tbg_sk_to_pk_ct): (pk48 [n, 48],
+        status [n] of KS_*).  A key that is zero or >= r has KS_ZERO / KS_RANGE and a
+        zero output."""
+        a = _u8(sk32, 32)
+        out = np.zeros((a.shape[0], 48), dtype=np.uint8)
+        st = np.zeros(a.shape[0], dtype=np.int32)
+        self._check(self._lib.tbg_sk_to_pk_ct(self._h, _ptr(a), a.shape[0], _ptr(out), _ptr(st)), "tbg_sk_to_pk_ct")
+        return out, st
+
+    def sign_ct(self, sk32, msgs, item_msg):
+        """tbls.Sign on the fixed schedule (tbg_sign_ct): (sig96 [n, 96], status [n] of KS_*)."""
+        a = _u8(sk32, 32)
+        data, off = msgs if isinstance(msgs, tuple) else pack_messages(msgs)
+        data, off, im = _u8(data), _u32(off), _u32(item_msg)
+        out = np.zeros((a.shape[0], 96), dtype=np.uint8)
+        st = np.zeros(a.shape[0], dtype=np.int32)
+        self._check(self._lib.tbg_sign_ct(self._h, _ptr(a), a.shape[0], _ptr(data), _ptr(off), len(off) - 1, _ptr(im),
+                                          _ptr(out), _ptr(st)), "tbg_sign_ct")
+        return out, st
 
 
     # ---- plain sums / FastAggregateVerify (DKG, cluster lock) ----

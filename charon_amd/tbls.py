@@ -9,7 +9,8 @@ parity test reads like ``tbls/tss_test.go``:
   verify_and_aggregate(tss, partial_sigs, msg)         tss.go:153-187
   TSS(pubshares, num_shares, threshold, public_key)    tss.go:62-116
   split_secret / combine_shares / generate_tss         tss.go:256-290, 220-253, 120-139
-  sign / partial_sign (test-only, not side-channel safe)  tss.go:200-217
+  sign / partial_sign (test-only, not side-channel safe unless
+  hardened=True)                                        tss.go:200-217
 
 plus the batch entry points the batch-aware call sites use:
 
@@ -17,6 +18,13 @@ plus the batch entry points the batch-aware call sites use:
   verify_and_aggregate_batch(duties) -> list[(Signature, signers) | TblsError]
   aggregate_batch(duties) -> list[Signature | TblsError]
   aggregate_and_verify_batch(duties) -> list[Signature | TblsError]
+
+and the hardened signer (tbg_sign_ct / tbg_sk_to_pk_ct: fixed-schedule scalar
+multiplication, key material wiped), for the keys of a create-cluster or DKG
+ceremony:
+
+  sign_batch(items) / partial_sign_batch(items) -> list[Signature | PartialSignature | TblsError]
+  secret_to_public_key_batch(secrets) -> list[PublicKey | TblsError]
 
 Keys and signatures are carried as their wire encodings (48-byte G1 /
 96-byte G2, ZCash-compressed); decoding, hashing, pairing and Lagrange
@@ -416,16 +424,18 @@ def _sk32(v: int) -> bytes:
     return (int(v) % R).to_bytes(32, "big")
 
 
-def split_secret(secret: int, t: int, n: int, rng, engine=None):
+def split_secret(secret: int, t: int, n: int, rng, engine=None, hardened=False):
     """tbls.SplitSecret (tss.go:256-290): n shares f(1..n) of f(x) = secret +
     a_1 x + ... + a_(t-1) x^(t-1) mod r, the a_j drawn from ``rng``
     (``randrange``), and the t Feldman commitments [a_j] g1 (48 bytes each,
     through Engine.sk_to_pk).  Host integers: NOT side-channel safe, and the
     engine's sk_to_pk is the test-only double-and-add of tbg_sk_to_pk -- not
-    for production keys."""
+    for production keys.  hardened=True forms the commitments on the fixed
+    schedule (tbg_sk_to_pk_ct); the polynomial is still split here on host
+    integers and keeps this warning -- the product's caller is Go, which
+    splits in kryptology."""
     shares, poly = _split_host(secret, t, n, rng)
-    commits = _engine(engine).sk_to_pk(b"".join(_sk32(c) for c in poly))
-    return shares, [bytes(c) for c in commits]
+    return shares, _sk_to_pk(poly, engine, hardened, "marshalling Secret Key")
 
 
 def _split_host(secret: int, t: int, n: int, rng):
@@ -445,16 +455,31 @@ def _split_host(secret: int, t: int, n: int, rng):
     return shares, poly
 
 
-def tss_from_shares(shares, commits, engine=None) -> TSS:
+def _sk_to_pk(scalars, engine, hardened, what):
+    """48-byte public keys of integer scalars: Engine.sk_to_pk, or with
+    hardened the fixed-schedule Engine.sk_to_pk_ct (a zero or out-of-range
+    scalar raises)."""
+    e = _engine(engine)
+    if not hardened:
+        return [bytes(k) for k in e.sk_to_pk(b"".join(_sk32(v) for v in scalars))]
+    pks, st = e.sk_to_pk_ct(b"".join(_sk32_exact(v) for v in scalars))
+    for s in st.tolist():
+        if s != eng.KS_OK:
+            raise TblsError(what + ": " + _KS_ERRORS.get(s, f"status {s}"))
+    return [bytes(k) for k in pks]
+
+
+def tss_from_shares(shares, commits, engine=None, hardened=False) -> TSS:
     """The TSS of a split whose scalar shares are at hand: pubshare i is
     sk_to_pk(f(i)) (what NewTSS's sum over the commitments evaluates to), the
     group key is C_0 and the threshold is the number of commitments.  Only
     for callers that hold the shares (GenerateTSS, create cluster): deriving
     the pubshares from the commitments alone (tbls.NewTSS proper) is not
-    implemented.  Test-only scalar multiplication, see split_secret."""
+    implemented.  Test-only scalar multiplication unless hardened, see
+    split_secret."""
     shares = list(shares)
     commits = [bytes(c) for c in commits]
-    pks = _engine(engine).sk_to_pk(b"".join(_sk32(s.value) for s in shares))
+    pks = _sk_to_pk([s.value for s in shares], engine, hardened, "unmarshal secret")
     ident = bytes([0xC0]) + bytes(47)
     if commits[0] == ident:
         raise TblsError("unmarshal pubkey: " + _PK_ERRORS[1])
@@ -466,16 +491,17 @@ def tss_from_shares(shares, commits, engine=None) -> TSS:
     return TSS(pub, len(shares), len(commits), PublicKey(commits[0]), tuple(commits))
 
 
-def generate_tss(t: int, n: int, rng, engine=None):
+def generate_tss(t: int, n: int, rng, engine=None, hardened=False):
     """tbls.GenerateTSS (tss.go:120-139): a random secret split t-of-n and its
     TSS.  Returns (TSS, shares, secret); the secret is returned for the parity
-    tests (the reference discards it).  Test clusters only: see split_secret."""
+    tests (the reference discards it).  Test clusters only: see split_secret
+    (hardened=True: every scalar multiplication on the fixed schedule)."""
     secret = rng.randrange(1, R)
     try:
-        shares, commits = split_secret(secret, t, n, rng, engine)
+        shares, commits = split_secret(secret, t, n, rng, engine, hardened=hardened)
     except TblsError as err:
         raise TblsError("generate secret shares: " + str(err))
-    return tss_from_shares(shares, commits, engine), shares, secret
+    return tss_from_shares(shares, commits, engine, hardened=hardened), shares, secret
 
 
 def combine_shares(shares, t: int, n: int) -> int:
@@ -503,14 +529,93 @@ def combine_shares(shares, t: int, n: int) -> int:
     return acc
 
 
-def sign(secret: int, msg: bytes, engine=None) -> Signature:
+def sign(secret: int, msg: bytes, engine=None, hardened=False) -> Signature:
     """tbls.Sign (tss.go:210-217) over Engine.sign.  TEST-ONLY like tbg_sign:
     a plain double-and-add whose timing depends on the key -- not side-channel
-    safe, never for a production validator key."""
+    safe, never for a production validator key.  hardened=True signs through
+    sign_batch (tbg_sign_ct) instead and raises its TblsError."""
+    if hardened:
+        r = sign_batch([(secret, msg)], engine)[0]
+        if isinstance(r, Exception):
+            raise r
+        return r
     return Signature(bytes(_engine(engine).sign(_sk32(secret), [bytes(msg)], [0])[0]))
 
 
-def partial_sign(share: SecretKeyShare, msg: bytes, engine=None) -> PartialSignature:
+def partial_sign(share: SecretKeyShare, msg: bytes, engine=None, hardened=False) -> PartialSignature:
     """tbls.PartialSign (tss.go:200-207) over Engine.sign.  TEST-ONLY like
-    tbg_sign: not side-channel safe, never for a production key share."""
+    tbg_sign: not side-channel safe, never for a production key share.
+    hardened=True signs through partial_sign_batch (tbg_sign_ct) instead."""
+    if hardened:
+        r = partial_sign_batch([(share, msg)], engine)[0]
+        if isinstance(r, Exception):
+            raise r
+        return r
     return PartialSignature(share.identifier, sign(share.value, msg, engine))
+
+
+# ------------------------------------------------------------ the hardened signer
+# tbg_sign_ct / tbg_sk_to_pk_ct (include/tbls_gpu.h): [sk]H(m) and [sk]G1 on a
+# fixed schedule -- the device's instruction and address streams do not depend
+# on the key, and the engine wipes every byte it allocated for keys.  The
+# Python integers and byte strings a caller holds are the caller's to guard.
+_KS_ERRORS = {
+    eng.KS_ZERO: "secret key cannot be zero",
+    eng.KS_RANGE: "secret key is not below the group order",
+    eng.KS_MSG: "hash to curve failed",
+}
+
+
+def _sk32_exact(v: int) -> bytes:
+    """32 big-endian bytes of v WITHOUT reduction mod r: the engine's range
+    check decides (KS_ZERO / KS_RANGE)."""
+    v = int(v)
+    if not 0 <= v < 1 << 256:
+        raise TblsError("unmarshal secret: secret key must be 32 bytes")
+    return v.to_bytes(32, "big")
+
+
+def sign_batch(items, engine=None):
+    """items: iterable of (secret, msg).  tbls.Sign for each in ONE launch of
+    the hardened signer; equal messages are sent (and hashed) once.  Returns
+    a Signature per item, or a TblsError: "unmarshal secret: ..." for a zero
+    or out-of-range secret (tblsconv.ShareToSecret / SecretFromBytes,
+    tblsconv.go:149-159), "sign: ..." (tss.go:213) when H(m) failed."""
+    items = list(items)
+    if not items:
+        return []
+    msgs, item_msg = _distinct_msgs([bytes(m) for _, m in items])
+    sigs, st = _engine(engine).sign_ct(b"".join(_sk32_exact(s) for s, _ in items), msgs, item_msg)
+    out = []
+    for sig, s in zip(sigs, st.tolist()):
+        if s == eng.KS_OK:
+            out.append(Signature(bytes(sig)))
+        else:
+            out.append(TblsError(("sign: " if s == eng.KS_MSG else "unmarshal secret: ") + _KS_ERRORS.get(s, f"status {s}")))
+    return out
+
+
+def partial_sign_batch(items, engine=None):
+    """items: iterable of (SecretKeyShare, msg).  tbls.PartialSign for each in
+    one launch of the hardened signer: a PartialSignature per item, or
+    sign_batch's TblsError ("partial sign: ..." when H(m) failed, tss.go:203)."""
+    items = list(items)
+    out = []
+    for (share, _), r in zip(items, sign_batch([(sh.value, m) for sh, m in items], engine)):
+        if isinstance(r, Exception):
+            out.append(TblsError(str(r).replace("sign: ", "partial sign: ", 1) if str(r).startswith("sign: ") else str(r)))
+        else:
+            out.append(PartialSignature(share.identifier, r))
+    return out
+
+
+def secret_to_public_key_batch(secrets, engine=None):
+    """SecretKey.GetPublicKey for many secrets in one launch of the hardened
+    signer: a PublicKey per secret, or TblsError("secret to pubkey: ...")
+    (cmd/createcluster.go:185-188) for a zero or out-of-range one."""
+    secrets = list(secrets)
+    if not secrets:
+        return []
+    pks, st = _engine(engine).sk_to_pk_ct(b"".join(_sk32_exact(s) for s in secrets))
+    return [PublicKey(bytes(pk)) if s == eng.KS_OK else TblsError("secret to pubkey: " + _KS_ERRORS.get(s, f"status {s}"))
+            for pk, s in zip(pks, st.tolist())]

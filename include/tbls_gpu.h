@@ -438,10 +438,44 @@ int tbg_fast_aggregate_verify(tbg_ctx* ctx, const uint32_t* pubkey_ids, const ui
  * timing depends on the key, so these entry points are not side-channel safe
  * and must not hold a production validator key (the Z inversions of the
  * results use the constant-time Fermat inversion, but that alone does not
- * make the path constant time). */
+ * make the path constant time).  A real key goes through tbg_sk_to_pk_ct /
+ * tbg_sign_ct below. */
 int tbg_sk_to_pk(tbg_ctx* ctx, const uint8_t* sk32, uint32_t n, uint8_t* pk48);
 int tbg_sign(tbg_ctx* ctx, const uint8_t* sk32, uint32_t n, const uint8_t* msgs, const uint32_t* msg_off,
              uint32_t n_msgs, const uint32_t* item_msg, uint8_t* sig96);
+
+/* The hardened signer: tbls.Sign / PartialSign and SecretKey.GetPublicKey for
+ * keys that matter (the create-cluster and DKG ceremonies: reference
+ * cmd/createcluster.go:185-207, :487-515, dkg/dkg.go:480-542).  Same
+ * arguments and the same results as tbg_sk_to_pk / tbg_sign, plus one
+ * TBG_KS_* code per item in status[] (required).
+ *
+ * [sk]G1 and [sk]H(m) run on a fixed schedule (csrc/bls_ctmul.h): sk is
+ * recoded into 64 signed 4-bit digits, and every window is 4 doublings, a
+ * masked scan of ALL nine table entries and one addition, in complete
+ * projective formulas that have no exceptional case -- 256 doublings and 64
+ * additions whatever the key is.  The result's Z is inverted by Fermat.
+ * CLAIMED: the instruction stream and the address stream (global memory, LDS,
+ * scratch) of the device code do not depend on sk; the host range check is a
+ * word-wise compare with no early exit; every device byte the engine
+ * allocated for keys and its pinned staging copy are overwritten with zeros
+ * on every exit path before they are released.
+ * NOT CLAIMED: power or electromagnetic leakage; isolation from other tenants
+ * of the device; that v_mad_u64_u32 (every field product) takes the same time
+ * for all operand values -- nobody has measured that, it is assumed; the
+ * wiping of registers and of compiler-placed scratch, which the engine cannot
+ * address; the caller's own copy of sk32.
+ *
+ * A key that is zero or >= r never reaches the device (1 is uploaded in its
+ * place): its output bytes are all zero and its code says why.  An item
+ * whose H(m) could not be formed gets TBG_KS_MSG and zero output. */
+#define TBG_KS_OK 0
+#define TBG_KS_ZERO (-40)   /* sk = 0                                  */
+#define TBG_KS_RANGE (-41)  /* sk >= r                                 */
+#define TBG_KS_MSG (-42)    /* the item's H(m) failed (tbg_sign_ct)    */
+int tbg_sk_to_pk_ct(tbg_ctx* ctx, const uint8_t* sk32, uint32_t n, uint8_t* pk48, int32_t* status);
+int tbg_sign_ct(tbg_ctx* ctx, const uint8_t* sk32, uint32_t n, const uint8_t* msgs, const uint32_t* msg_off,
+                uint32_t n_msgs, const uint32_t* item_msg, uint8_t* sig96, int32_t* status);
 
 /* Last kernel timings of the context (milliseconds, HIP events on the
  * engine's streams): [decode, hash, combine (RLC sums + group lines),
