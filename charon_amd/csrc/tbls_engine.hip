@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 #include "tbls_launch.h"
+#include "tbls_plan.h"
 #include "bls_l0msg.h"
 #include "bls_lines.h"
 
@@ -66,8 +67,6 @@ namespace {
 
 constexpr int kChainEvents = 11;
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // One caller batch inside a slot: tbg_submit_group packs several batches into
 // one device batch (one launch per kernel for all of them); each keeps its
 // own ticket and its slice of the outputs.
@@ -86,7 +85,6 @@ struct Slot {
   bool express = false;     // the high-priority slot of small batches (tbg_config.express_partials)
   std::vector<Part> parts;
   tbg_ticket ticket = 0;    // first part's ticket (LRU order of the slots)
-  uint32_t op = 0, n_duties = 0, n_partials = 0, n_msgs = 0;
   // pinned host staging
   uint8_t* h_in = nullptr;
   size_t h_in_cap = 0;
@@ -97,7 +95,6 @@ struct Slot {
   size_t d_in_cap = 0;
   uint8_t* d_work = nullptr;
   size_t d_work_cap = 0;
-  size_t out_bytes = 0;
   hipStream_t st = nullptr;   // per-signature chain (decode, lines, verify, aggregate)
   hipStream_t st2 = nullptr;  // per-message chain (hash_to_G2, H(m) lines), joins st before verify
   hipEvent_t ev[kChainEvents] = {};  // see launch_chain
@@ -108,17 +105,13 @@ struct Slot {
   tbg::DevBatch B{};           // device view of the last batch (resident until the slot is reused)
   tbg::DevBatch last{};        // the batch as its last run launched it (a replay's prefix and shape):
                                // what tbg_fetch_stats / _fallback / _shape / _subgroup describe
-  size_t w_out = 0;
-  uint32_t sgb_m_small = 0;    // the group size of a prefix below sgb_tri_partials (its arena holds both layouts)
-  // a set launch (tbg_submit_sets): its one part spans the padded device batch
-  bool sets = false;
-  uint32_t n_sets = 0;
-  size_t o_sets = 0;           // set_status in the output image
+  tbg::LaunchLayout L{};       // the batch's counts and plan, and where its sections lie in the arenas (tbls_plan.h)
 };
 
 }  // namespace
 
-struct tbg_ctx {
+// (PlanConfig: the fields that planning reads, tbls_plan.h)
+struct tbg_ctx : tbg::PlanConfig {
   int device = 0;
   hipStream_t stream = nullptr;  // utility stream (pubkey table, test-vector generation)
   std::mutex mu;
@@ -132,32 +125,13 @@ struct tbg_ctx {
   std::vector<Slot> slots;
   tbg_ticket next_ticket = 1;
   float last_ms[8] = {};
-  // Defaults measured on MI355X (tools/sweep_rlc.sh, config 2): 16 duties per
-  // level-1 group, 4 per Miller quad beat 8 / 2 by ~8 %: half the final
-  // exponentiations and Fp12 squarings per duty.
-  uint32_t rlc_group = 16;  // 0 = per-partial checks (TBG_VERIFY_EACH)
-  uint32_t rlc_chunk = 4;
-  bool chunk_auto = true;    // rlc_chunk not configured: level-0 launches of many duties take 8
-  bool rlc_auto = false;     // rlc_group follows the observed invalid share (tbg_config.rlc_group = 0)
-  uint32_t rlc_batch = TBG_RLC_L0_AUTO;  // level 0 (the whole device batch as one check)
-  double invalid_ema = 0.0;  // exponential average of the invalid share of collected verified partials
   uint64_t rlc_seed = 0;   // 0 = OS randomness per batch
   uint64_t seed_ctr = 0;
-  uint32_t gident = TBG_GIDENT_OFF;  // level 1g routing (tbg_config.gident)
-  uint32_t fb_window = TBG_FB_WINDOW;  // fallback line buffer positions per pass (tbg_config.fb_window)
-  uint32_t sgb_mode = TBG_SGB_AUTO;    // batched subgroup test (tbg_config.subgroup_batch)
   uint32_t express_max = TBG_EXPRESS_PARTIALS;  // batches up to this many partials prefer the express slot
-  uint32_t l0_duty_partials = TBG_L0_DUTY_PARTIALS;  // fused level 0: P_d per duty from this many partials (tbg_config.l0_duty_partials)
-  uint32_t l0_tail_partials = TBG_L0_TAIL_PARTIALS;  // fused level 0: S inside the key-side grid from this many partials (tbg_config.l0_tail_partials)
-  uint32_t l0_msg_share = TBG_L0_MSG_SHARE;  // fused level 0: per message from this many duties per message (tbg_config.l0_msg_share)
-  uint32_t sgb_tri_partials = TBG_SGB_TRI_PARTIALS;  // batched subgroup test: triple schedule from this many partials (tbg_config.sgb_tri_partials)
-  uint32_t sgb_tri_m = SGB_TRI_M;                    // its group size (tbg_config.sgb_tri_m)
-  uint32_t n_simd = 1024;  // SIMDs of the device (CUs x 4): the level-0 shape rule's unit (l0_shape)
   // host-side work of the submit / collect calls (tbg_host_stats): [submits,
   // partials submitted, pack ns, enqueue ns, collects, partials collected,
   // gather ns, wait ns]
   std::atomic<uint64_t> host[8] = {};
-  double nonsub_ema = 0.0;  // exponential average of the non-subgroup share of collected partials
 };
 
 #define HIP_TRY(x)                       \
@@ -634,389 +608,85 @@ int tbg_submit_sets(tbg_ctx* c, const tbg_batch* b, const uint32_t* set_first, u
   return submit_impl(c, &b, 1, ticket, set_first, n_sets);
 }
 
-// Level-0 launch shape.  The level-0 Miller kernel's
-// waves are long -- one hexad = the whole 68-step loop over C duties -- and
-// issue-bound at ONE wave per SIMD: a lone wave runs its loop in 3.6 ms at
-// C = 4, two sharing a SIMD take 6.8 ms each (profiles/r05/waves), so the
-// kernel's time is ~ceil(waves / SIMDs) hexad lengths, and a launch whose
-// waves spill just past a multiple of the SIMD count pays a whole hexad
-// length for the remainder: config 4's 125k-duty shard at (G, C) = (16, 4)
-// is 3,126 waves on 1,024 SIMDs.  A hexad of C duties costs 62 squarings +
-// 68 C line products, w(C) = 0.95 M + 1.39 M C u32 mul-adds
-// (profiles/work_model.json, l0_chunk_*), so fewer, longer hexads win where
-// they save a unit: (16, 8) halves the squarings, (14, 7) runs 125k duties
-// in 2 units instead of 4.  The rule picks the cheapest of (16, 4), (16, 8),
-// (14, 7) by ceil(waves / SIMDs) x w(C) -- 100k duties keep (16, 4), 125k
-// take (14, 7), 160k (16, 8), as the A/B runs of profiles/r05/chunk8_ab,
-// shape_ab and sqrt_x2_ab measured best.  A configured group size G keeps G
-// (C = 4 or 8 only).  tbg_replay_plan applies it to the duties of the
-// launches it runs together (their Miller kernels share the SIMDs).
-static double l0_shape_cost(uint64_t nd, uint32_t n_simd, uint32_t g, uint32_t ch) {
-  const uint64_t hexads = (uint64_t)((nd + g - 1) / g) * ((g + ch - 1) / ch);
-  const uint64_t waves = (hexads + 9) / 10;
-  return (0.948 + 1.395 * ch) * (double)((waves + n_simd - 1) / n_simd);
-}
-// Round 6: with the group size free, every chunk C of
-// 5 .. 10 duties is a candidate too, as (G, C) = (C, C) -- one chunk per
-// group -- so the hexads can fill whole wave-slot rounds: the 20-step plan's
-// 200k duties take (10, 10) (2,000 waves: 2 rounds) instead of (14, 7) (2,858
-// waves: 3 rounds; +2.6 % at the driver shape, profiles/r06/shape), config
-// 3's 100k (10, 10) instead of (16, 4) (Miller 8.0 vs 9.4 ms).  Chunks of 13
-// and 16 duties were measured far off the model (a round of ~1,000 lone
-// waves: (16, 16) 20.4 ms vs (16, 8) 12.2 ms at 160k duties, (13, 13) 16.8
-// vs (14, 7) 11.0 ms at 125k: the C line loads of a step are not hidden by a
-// second wave), so C stops at L0_SHAPE_MAX_C.
-// `fits` (a replay's arenas, below) drops the candidates a launch cannot hold.
-static bool l0_fits_any(uint32_t, uint32_t) { return true; }
-static void l0_shape(uint64_t nd, uint32_t n_simd, bool g_free, uint32_t& G, uint32_t& C,
-                     const std::function<bool(uint32_t, uint32_t)>& fits) {
-  C = 4;
-  if (G < 8) return;
-  constexpr uint32_t L0_SHAPE_MAX_C = 10;
-  uint32_t cand[3 + L0_SHAPE_MAX_C][2] = {{g_free ? 16u : G, 4}, {g_free ? 16u : G, 8}, {14, 7}};
-  uint32_t n_cand = g_free ? 3u : 2u;
-  for (uint32_t c = 5; g_free && c <= L0_SHAPE_MAX_C; ++c) {
-    cand[n_cand][0] = c;
-    cand[n_cand][1] = c;
-    ++n_cand;
-  }
-  double best = 1e300;
-  const uint32_t G0 = G;
-  for (uint32_t k = 0; k < n_cand; ++k) {
-    if (!fits(cand[k][0], cand[k][1])) continue;
-    const double cost = l0_shape_cost(nd, n_simd, cand[k][0], cand[k][1]);
-    if (cost < best - 1e-9) {
-      best = cost;
-      G = cand[k][0];
-      C = cand[k][1];
-    }
-  }
-  if (best == 1e300) G = G0;  // (nothing fits: the caller keeps its shapes)
-}
-// A launch of nd duties (a prefix of its slot's device batch) at (G, C) fits
-// the slot's arena, whose group / chunk sections were sized at submit for
-// the slot's nd0 duties at (G0, C0) (tbg_submit_group).
-static bool l0_shape_fits(uint32_t nd0, uint32_t G0, uint32_t C0, uint32_t nd, uint32_t G, uint32_t C) {
-  const uint64_t ng0 = (nd0 + G0 - 1) / G0, nch0 = (G0 + C0 - 1) / C0;
-  const uint64_t ng = (nd + G - 1) / G, nch = (G + C - 1) / C;
-  // every group / chunk section of the arena (tbg_submit_group's w_cf,
-  // w_gidf: ng (nch + 1); w_cl, w_cfe, w_cidl: ng nch -- ADVICE r05: the
-  // max() below alone let nd0 hide an overflow of these; w_cidp: ng nch C;
-  // w_gidp: ng G; w_pend: max(ng nch, nd); grp_f: ng)
-  return ng <= ng0 && ng * (nch + 1) <= ng0 * (nch0 + 1) && ng * nch <= ng0 * nch0 && ng * nch * C <= ng0 * nch0 * C0 &&
-         ng * G <= ng0 * G0 && std::max(ng * nch, (uint64_t)nd) <= std::max(ng0 * nch0, (uint64_t)nd0) &&
-         (G <= 64) == (G0 <= 64);
-}
+// ---- submit_impl's steps, in its order.  What a launch decides (plan_launch)
+// and where its sections lie (layout, bind) is tbls_plan.h's. ----
 
-// Batched subgroup test plan from the non-subgroup share `rho` of the
-// collected partials.  Per signature, in units of one
-// per-signature test (psi(s) == [x] s: 63 doublings + 5 additions): the 16.6
-// bucket additions with the sort and running sums 0.55 (measured: k_sgb_*
-// 0.47-0.57 of k_subgroup_sigs' time per signature, profiles/r06/sgb), the
-// group's 18 tests 1.1 x 18 / m (each on a lone lane pair), and the failed
-// groups' members tested alone 1 - (1 - rho)^m.  The group size m is the
-// cheapest power of two in [SGB_M_MIN, SGB_M]; the test runs while that
-// costs under 0.95 of testing every signature alone -- up to rho ~ 2.5e-3
-// (TBG_SGB_AUTO_MAX).  Clean traffic keeps m = 1,024; config 5's 1.25e-3
-// takes m = 128 (at 1,024, 72 % of its groups would fail).  The 0.55 is the
-// classic schedule's; the paired schedule of groups >= SGB_PAIR_M
-// (tbls_launch.h) is cheaper, which only widens the test's margin, and the
-// sizes this plan picks are left as they were.
-static bool sgb_plan(double rho, uint32_t& m) {
-  double best = 1e9;
-  m = SGB_M;
-  for (uint32_t k = SGB_M; k >= SGB_M_MIN; k >>= 1) {
-    const double cost = 0.55 + 1.1 * (double)SGB_K / k + (1.0 - std::pow(1.0 - std::min(rho, 1.0), (double)k));
-    if (cost < best - 1e-12) {
-      best = cost;
-      m = k;
-    }
-  }
-  return best < 0.95;
-}
+// The caller batches of one submit.
+struct SubmitInput {
+  const tbg_batch* const* bs;
+  uint32_t n_batches;
+  const uint32_t* set_first;  // a set launch (one batch), else null
+  uint32_t n_sets;
+};
 
-// The triple schedule (tbls_launch.h sgb_triple) in the same units.  Whether
-// its arithmetic pays at a launch's size is the threshold's business
-// (tbg_config.sgb_tri_partials, set from an A/B like l0_duty_partials): the
-// count model (tools/sgb_pair_model.py) has bucket
-// additions, ranked slots and reductions at 7.30 per member in groups of
-// 16,384 against the paired 11.66 at 1,024, so 0.55 x (1 - 7.30 / 11.66) =
-// 0.21 less per signature.  What the plan weighs is the term that grows with
-// the group: a failed group's members are tested alone, 1 - (1 - rho)^m of
-// them, against the same term at the size `m_small` that sgb_plan picked.
-// The triple schedule runs while that difference stays under the modelled
-// saving -- rho up to ~1.4e-5 at 16,384, the clean regime; any measurable
-// non-subgroup share falls back to the paired sizes exactly as before.
-static bool sgb_plan_triple(double rho, uint32_t m_small, uint32_t m_tri) {
-  const double r = std::min(rho, 1.0);
-  const double extra = std::pow(1.0 - r, (double)m_small) - std::pow(1.0 - r, (double)m_tri) +
-                       1.1 * (double)SGB_K * (1.0 / m_tri - 1.0 / m_small);
-  return extra < 0.55 * (1.0 - 7.30 / 11.66);
-}
-// The launch's group size: sgb_plan's, or the triple schedule's in a clean
-// launch of at least sgb_tri_partials partials.  (A replayed prefix asks
-// again with its own partial count.)
-static uint32_t sgb_group_size(const tbg_ctx* c, uint32_t np, uint32_t m_small, bool clean_tri) {
-  return clean_tri && np >= c->sgb_tri_partials ? c->sgb_tri_m : m_small;
-}
-
-// Device duties of a set launch at group size G: every non-empty set starts on
-// a multiple of G (the duties between are empty padding), so no level-1 group
-// holds duties of two sets.
-static uint64_t sets_padded(const uint32_t* set_first, uint32_t n_sets, uint32_t G) {
-  uint64_t e = 0;
-  for (uint32_t k = 0; k < n_sets; ++k) {
-    const uint32_t n = set_first[k + 1] - set_first[k];
-    if (n) e = (e + G - 1) / G * G + n;
-  }
-  return e;
-}
-
-static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches, tbg_ticket* tickets,
-                       const uint32_t* set_first, uint32_t n_sets) {
-  if (!c || !bs || !tickets || n_batches == 0) return TBG_E_INVALID_ARG;
+// Validate the batches and total their counts (d) and per-batch duties and
+// messages (dm, plan_launch's batch_dm).
+static int total_inputs(const SubmitInput& in, LaunchDims& d, std::vector<uint32_t>& dm) {
   int rc;
-  for (uint32_t k = 0; k < n_batches; ++k) {
-    if ((rc = validate(bs[k])) != TBG_OK) return rc;
-    if (bs[k]->op != bs[0]->op) return TBG_E_INVALID_ARG;  // one kernel chain per device batch
+  for (uint32_t k = 0; k < in.n_batches; ++k) {
+    if ((rc = validate(in.bs[k])) != TBG_OK) return rc;
+    if (in.bs[k]->op != in.bs[0]->op) return TBG_E_INVALID_ARG;  // one kernel chain per device batch
   }
-  const uint32_t op = bs[0]->op;
-  const bool verify = op != TBG_OP_AGGREGATE;
-  // TBG_OP_AGGREGATE_VERIFY: the checks run on the batch's view (aggver_view), one
-  // candidate per duty, so every array of the check levels is sized by duties (vp below)
-  // and the per-duty key ids are packed by duty count
-  const bool aggver = op == TBG_OP_AGGREGATE_VERIFY;
-  if (aggver && set_first) return TBG_E_INVALID_ARG;
+  d.op = in.bs[0]->op;
+  const bool verify = d.op != TBG_OP_AGGREGATE;
+  if (d.op == TBG_OP_AGGREGATE_VERIFY && in.set_first) return TBG_E_INVALID_ARG;
   uint64_t nd64 = 0, np64 = 0, nm64 = 0, mb64 = 0;
-  for (uint32_t k = 0; k < n_batches; ++k) {
-    nd64 += bs[k]->n_duties;
-    np64 += bs[k]->n_partials;
+  for (uint32_t k = 0; k < in.n_batches; ++k) {
+    const tbg_batch* b = in.bs[k];
+    nd64 += b->n_duties;
+    np64 += b->n_partials;
     if (verify) {
-      nm64 += bs[k]->n_msgs;
-      mb64 += bs[k]->msg_off[bs[k]->n_msgs];
+      nm64 += b->n_msgs;
+      mb64 += b->msg_off[b->n_msgs];
     }
+    dm.push_back(b->n_duties);
+    dm.push_back(b->n_msgs);
   }
   if (np64 > 0x7FFFFFFFull || nd64 > 0x7FFFFFFFull || nm64 > 0x7FFFFFFFull || mb64 > 0xFFFFFFFFull)
     return TBG_E_INVALID_ARG;
-  std::unique_lock<std::mutex> lk(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  // Least recently used free slot: a collected batch stays resident (for
-  // tbg_replay / tbg_fetch) until every other slot has been reused.  A batch
-  // of at most express_max partials takes the express slot when it is free.
+  d.n_duties = (uint32_t)nd64;
+  d.n_partials = (uint32_t)np64;
+  d.n_msgs = (uint32_t)nm64;
+  d.msg_bytes = (size_t)mb64;
+  d.sets = in.set_first != nullptr;
+  d.n_sets = d.sets ? in.n_sets : 0;
+  return TBG_OK;
+}
+
+// Least recently used free slot: a collected batch stays resident (for
+// tbg_replay / tbg_fetch) until every other slot has been reused.  A batch
+// of at most express_max partials takes the express slot when it is free.
+static Slot* free_slot(tbg_ctx* c, uint32_t n_partials) {
   Slot* s = nullptr;
-  const bool small = np64 <= c->express_max;
+  const bool small = n_partials <= c->express_max;
   for (auto& x : c->slots)
     if (x.express && small && !x.busy) s = &x;
   if (!s)
     for (auto& x : c->slots)
       if (!x.express && !x.busy && (!s || x.ticket < s->ticket)) s = &x;
-  if (!s) return TBG_E_BUSY;
+  return s;
+}
 
-  const uint32_t np = (uint32_t)np64, nm = (uint32_t)nm64;
-  const size_t msg_bytes = (size_t)mb64;
-  if (c->rlc_auto)
-    c->rlc_group = c->invalid_ema < TBG_RLC_AUTO_TO8 ? 16 : c->invalid_ema < TBG_RLC_AUTO_TO4 ? 8 : 4;
-  uint32_t G = verify ? c->rlc_group : 0;
-  if (set_first) {
-    // An unconfigured group size shrinks (to 8, then 4) while the sets'
-    // padding would pass 1/8 of the duties: a launch of small sets keeps its
-    // groups full instead of checking mostly padding.
-    while (c->rlc_auto && G > 4 && sets_padded(set_first, n_sets, G) > nd64 + nd64 / 8) G /= 2;
-    nd64 = sets_padded(set_first, n_sets, G ? G : 1);  // (>= the caller's duties: validate() wants one at least)
-    if (nd64 > 0x7FFFFFFFull) return TBG_E_INVALID_ARG;
-  }
-  const uint32_t nd = (uint32_t)nd64;
-  const uint32_t vp = aggver ? nd : np;  // candidates of the check levels
+static int grow_slot(Slot* s, const LaunchLayout& L) {
+  int rc;
+  if ((rc = grow_pinned(&s->h_in, &s->h_in_cap, L.in_bytes)) != TBG_OK) return rc;
+  if ((rc = grow_pinned(&s->h_out, &s->h_out_cap, L.out_bytes)) != TBG_OK) return rc;
+  if ((rc = grow_device(&s->d_in, &s->d_in_cap, L.in_bytes)) != TBG_OK) return rc;
+  return grow_device(&s->d_work, &s->d_work_cap, L.work_bytes);
+}
 
-  // ---- input arena layout (16-byte aligned sections) ----
-  size_t o = 0;
-  auto sec = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 16); return at; };
-  size_t o_msgs = sec(msg_bytes);
-  size_t o_msg_off = sec(4ull * (nm + 1));
-  size_t o_duty_msg = sec(4ull * nd);
-  size_t o_duty_first = sec(4ull * (nd + 1));
-  size_t o_thr = sec(4ull * nd);
-  size_t o_pduty = sec(4ull * np);
-  size_t o_sigs = sec(96ull * np);
-  size_t o_ids = sec(np);
-  size_t o_pk = sec(4ull * vp);
-  size_t o_dset = sec(set_first ? 4ull * nd : 0);
-  size_t o_iota = sec(aggver ? 4ull * (nd + 1) : 0);
-  // Level 0 by message (bls_l0msg.h): the duties sorted by message and the
-  // chunk plan, packed with the inputs.  Reserved whenever a fused level 0
-  // may run with the knob on, whatever the launch's own duties per message:
-  // a replayed prefix decides from its own (l0_by_msg).  The work arena's
-  // sections follow below, once `fused` is known; this side is sized by the
-  // same conditions except the subgroup test's, which only shrink it.
-  // Nothing is reserved or sorted when no prefix of the caller batches
-  // reaches the share (one message per duty: the headline workload).
-  bool l0m_in = false;
-  if (verify && !aggver && c->rlc_group != 0 && c->rlc_batch != TBG_RLC_L0_OFF && c->sgb_mode != TBG_SGB_OFF &&
-      c->l0_msg_share != TBG_L0_MSG_NEVER && np >= SGB_MIN_PARTIALS) {
-    uint64_t cd = 0, cm = 0;
-    for (uint32_t k = 0; k < n_batches; ++k) {
-      cd = set_first ? nd : cd + bs[k]->n_duties;
-      cm += bs[k]->n_msgs;
-      l0m_in = l0m_in || cm * c->l0_msg_share <= cd;
-    }
-  }
-  const size_t l0m_chunks = l0m_in ? (size_t)l0m_chunk_bound(nm, nd) : 0;
-  size_t o_mfirst = sec(l0m_in ? 4ull * (nm + 1) : 0);
-  size_t o_mduty = sec(l0m_in ? 4ull * nd : 0);
-  size_t o_cfirst = sec(l0m_in ? 4ull * (nm + 1) : 0);
-  size_t o_cmsg = sec(l0m_in ? 4ull * l0m_chunks : 0);
-  size_t in_bytes = o;
-  // ---- work/output arena ----
-  o = 0;
-  size_t w_sig_aff = sec(sizeof(G2A) * (size_t)np);
-  size_t w_h_aff = sec(sizeof(G2A) * (size_t)nm);
-  size_t w_h_st = sec(4ull * nm);
-  size_t w_h_jac = sec(3 * sizeof(G2J) * (size_t)nm);  // H(m) + the cofactor clearing's two temporaries
-  size_t w_lam = sec(32ull * np);
-  // The fallback levels' lines share one buffer of fb_w list positions,
-  // consumed in passes (DevBatch::fb_window): a slot no longer holds 22.8 KB
-  // per partial for lists that a clean batch leaves empty.
-  const uint32_t fb_w = verify ? std::max<uint32_t>(1u, std::min<uint32_t>(c->fb_window, vp)) : 0u;
-  size_t w_sl = sec(4ull * LINES_WORDS * fb_w);
-  size_t w_hl = sec(4ull * LINES_WORDS * nm);
-  // Level 0 while the collected batches are clean (or as configured): one
-  // failed level-0 check costs its own work on top of the group levels.
-  const bool l0 = G != 0 && vp < (1u << 28) &&
-                  (c->rlc_batch == TBG_RLC_L0_ON || (c->rlc_batch == TBG_RLC_L0_AUTO && c->invalid_ema < TBG_RLC_AUTO_L0));
-  uint32_t C = c->rlc_chunk;
-  // (a set launch keeps its G: the sets are padded to it)
-  if (l0 && c->chunk_auto) l0_shape(nd, c->n_simd, !set_first && c->rlc_auto && G == 16, G, C, l0_fits_any);
-  if (C > G) C = G ? G : 1;
-  const uint32_t ng = G ? (nd + G - 1) / G : 0;
-  const uint32_t nch = G ? (G + C - 1) / C : 0;
-  size_t w_pp = sec(G ? sizeof(G1J) * (size_t)vp : 0);
-  size_t w_ps = sec(G ? sizeof(G2J) * (size_t)vp : 0);
-  size_t w_cf = sec(G ? 4ull * 3 * 4 * NL * ng * (nch + 1) : 0);
-  size_t w_cl = sec(G > 1 ? 4ull * ng * nch : 0);
+// ---- pack: no HIP call, no lock.  H is the launch's sections in the pinned
+// input image (bind over h_in), which is the packers' to write. ----
 
-  size_t w_dvp = sec(G ? sizeof(G1A) * (size_t)nd : 0);
-  size_t w_dvs = sec(G ? sizeof(G2J) * (size_t)nd : 0);
-  size_t w_dvst = sec(G ? 4ull * nd : 0);
-  size_t w_gst = sec(4ull * ng);
-  size_t w_gl = sec(4ull * LINES_WORDS * ng);
-  size_t w_cnt = sec(4ull * CNT_WORDS);
-  size_t w_pl = sec(verify ? 4ull * vp : 0);
-  size_t w_dvfe = sec(G > 1 ? 4ull * 3 * 4 * NL * nd : 0);
-  size_t w_pend = sec(G ? sizeof(G2A) * (size_t)std::max<size_t>(std::max<size_t>(ng, (size_t)ng * nch), nd) : 0);
-  size_t w_cfe = sec(G > 1 ? 4ull * 3 * 4 * NL * ng * nch : 0);
-  size_t w_cidl = sec(G > 1 ? 4ull * ng * nch : 0);
-  size_t w_cidp = sec(G > 1 ? sizeof(G1A) * (size_t)ng * nch * C : 0);
-
-  size_t w_gfe = sec(G > 1 ? 4ull * 3 * 4 * NL * ng : 0);
-  size_t w_gidl = sec(G > 1 ? 4ull * ng : 0);
-  size_t w_gidp = sec(G > 1 ? sizeof(G1A) * (size_t)ng * G : 0);
-  size_t w_gidf = sec(G > 1 ? 4ull * 3 * 4 * NL * ng * (nch + 1) : 0);
-  size_t w_idl = sec(G > 1 ? 4ull * nd : 0);
-  size_t w_idp = sec(G > 1 ? sizeof(G1A) * (size_t)nd : 0);
-  size_t w_bpt = sec(l0 ? sizeof(G2A) : 0);
-  size_t w_blines = sec(l0 ? 4ull * LINES_WORDS : 0);
-  size_t w_bf = sec(l0 ? 4ull * 3 * 4 * NL : 0);
-  size_t w_gf = sec(l0 ? 4ull * 3 * 4 * NL * grp_f_entries(ng) : 0);
-  // level 1's group MSM (k_gmsm.hip): entries, offsets, bucket sums, leads, the failed groups' candidates
-  size_t w_gmoff = sec(G ? 4ull * (GM_BUCKETS + 1) * ng : 0);
-  size_t w_gment = sec(G ? 64ull * vp : 0);
-  size_t w_gmpart = sec(G ? sizeof(G2J) * GM_BUCKETS * (size_t)ng : 0);
-  size_t w_gmlead = sec(G ? 4ull * ng : 0);
-  size_t w_gmlist = sec(G ? 4ull * vp : 0);
-  size_t w_gmhist = sec(G ? 4ull * 256 : 0);
-  size_t w_gmorder = sec(G ? 4ull * GM_BUCKETS * ng : 0);
-  // Batched subgroup test while the collected batches carry (almost) no
-  // non-subgroup signature: groups of 1,024 partials, a failed group's members
-  // tested alone (k_sgb.hip); small batches test every signature alone.
-  uint32_t sgb_m = SGB_M;
-  const bool sgb = np >= SGB_MIN_PARTIALS && c->sgb_mode != TBG_SGB_OFF &&
-                   (sgb_plan(c->nonsub_ema, sgb_m) || c->sgb_mode == TBG_SGB_ON);
-  // A clean launch of at least sgb_tri_partials partials takes the triple
-  // schedule's large groups.  A replayed prefix below the threshold goes back
-  // to sgb_m_small, so such a launch's sections hold either layout.
-  const uint32_t sgb_m_small = sgb_m;
-  const bool sgb_tri_ok = sgb && sgb_plan_triple(c->nonsub_ema, sgb_m_small, c->sgb_tri_m);
-  sgb_m = sgb_group_size(c, np, sgb_m_small, sgb_tri_ok);
-  const bool sgb_tri = sgb_triple(sgb_m);
-  const uint32_t sgb_split = sgb_tri ? 1u : sgb_split_for(sgb_m);
-  const size_t n_sg = sgb ? sgb_groups(np, sgb_m) : 0;
-  const size_t n_sg_small = sgb ? sgb_groups(np, sgb_m_small) : 0;  // (the most groups a prefix can have)
-  auto sgsec = [&](auto&& per_group) {  // a section of per_group(m) units per group, in either layout
-    return std::max<size_t>(per_group(sgb_m) * n_sg, sgb_tri ? per_group(sgb_m_small) * n_sg_small : 0);
-  };
-  size_t w_sgoff = sec(4ull * sgsec([](uint32_t m) { return (size_t)sgb_off_stride(m); }));
-  size_t w_sgent = sec(4ull * sgsec([](uint32_t m) { return (size_t)sgb_ent_stride(m); }));
-  size_t w_sgpart = sec(sizeof(G2J) * sgsec([](uint32_t m) { return (size_t)sgb_part_stride(m); }));
-  size_t w_sgrank = sec(4ull * sgsec([](uint32_t m) { return (size_t)sgb_rank_stride(m); }));
-  size_t w_sgcode = sec(sgb_tri ? 4ull * SGB_TRIPLES * np : 0);
-  size_t w_sgbad = sec(4ull * std::max(n_sg, sgb_tri ? n_sg_small : 0));
-  // Level 0's signature side: with the batched test on, S comes from the
-  // test's sums (l0_fused, tbls_launch.h; a replayed prefix of the launch
-  // keeps both flags, so it takes the same path) and the bucket MSM's
-  // arrays are not needed; otherwise the bucket MSM of k_msm.hip.
-  // (TBG_OP_AGGREGATE_VERIFY: the subgroup test is the partials', the level 0 the view's,
-  // which has no digits to take S from -- always the bucket MSM, over the duties)
-  const bool fused = l0 && sgb && !aggver;
-  const bool msm = l0 && !fused;
-  size_t w_mr = sec(msm ? 8ull * vp : 0);
-  size_t w_moff = sec(msm ? 4ull * (MSM_BUCKETS + 1) : 0);
-  size_t w_mcur = sec(msm ? 4ull * MSM_BUCKETS : 0);
-  size_t w_ment = sec(msm ? 16ull * vp : 0);
-  size_t w_mbkt = sec(msm ? sizeof(G2J) * (size_t)MSM_BUCKETS : 0);
-  size_t w_mpart = sec(msm ? sizeof(G2J) * (size_t)MSM_BUCKETS * MSM_SPLIT : 0);
-  size_t w_msum = sec(msm ? sizeof(G2J) * (size_t)MSM_SUM_ENTRIES : 0);
-  size_t w_sgt = sec(fused ? sizeof(G2J) * sgsec([](uint32_t m) { return (size_t)sgb_t_slices(m); }) : 0);
-  size_t w_l0fsum = sec(fused ? sizeof(G2J) * std::max<size_t>(l0f_sum_entries((uint32_t)n_sg, sgb_m),
-                                                               sgb_tri ? l0f_sum_entries((uint32_t)n_sg_small, sgb_m_small) : 0)
-                              : 0);
-  size_t w_l0fu = sec(fused ? 16ull * np : 0);
-  // level 0 by message: chunk sums and their member counts, Q_m, the messages' states
-  const bool l0m = fused && l0m_in;
-  size_t w_l0mpart = sec(l0m ? sizeof(G1J) * l0m_chunks : 0);
-  size_t w_l0mcnt = sec(l0m ? 4ull * l0m_chunks : 0);
-  size_t w_l0mq = sec(l0m ? sizeof(G1A) * (size_t)nm : 0);
-  size_t w_l0mst = sec(l0m ? 4ull * nm : 0);
-  size_t w_aacc = sec(op != TBG_OP_VERIFY ? sizeof(G2J) * (size_t)nd : 0);
-  size_t w_alist = sec(op != TBG_OP_VERIFY ? 4ull * nd : 0);
-  size_t w_aaff = sec(aggver ? sizeof(G2A) * (size_t)nd : 0);
-  size_t w_avst = sec(aggver ? 4ull * nd : 0);
-  size_t w_avcnt = sec(aggver ? 4ull * CNT_WORDS : 0);
-  size_t w_out = o;  // outputs are contiguous so one D2H copy brings them back
-  size_t w_pst = sec(4ull * np);
-  size_t w_dst = sec(4ull * nd);
-  size_t w_agg = sec(96ull * nd);
-  size_t w_sst = sec(set_first ? 4ull * ((size_t)n_sets + SET_TAIL) : 0);
-  size_t work_bytes = o;
-  size_t out_bytes = work_bytes - w_out;
-
-  if ((rc = grow_pinned(&s->h_in, &s->h_in_cap, in_bytes)) != TBG_OK) return rc;
-  if ((rc = grow_pinned(&s->h_out, &s->h_out_cap, out_bytes)) != TBG_OK) return rc;
-  if ((rc = grow_device(&s->d_in, &s->d_in_cap, in_bytes)) != TBG_OK) return rc;
-  if ((rc = grow_device(&s->d_work, &s->d_work_cap, work_bytes)) != TBG_OK) return rc;
-  // Reserve the slot (busy, its old tickets expired) and pack WITHOUT the
-  // context lock: a 16-batch group is ~70 MB of host copies, during which
-  // other threads' tbg_poll / tbg_collect / tbg_submit must not wait.
-  s->parts.clear();
-  s->busy = true;
-  lk.unlock();
-  const auto t_pack = std::chrono::steady_clock::now();
-
-  // ---- pack: batch k's duties / partials / messages follow batch k-1's,
-  // every index rebased by the running offsets ----
-  uint8_t* h = s->h_in;
-  uint32_t* msg_off = (uint32_t*)(h + o_msg_off);
-  uint32_t* duty_msg = (uint32_t*)(h + o_duty_msg);
-  uint32_t* duty_first = (uint32_t*)(h + o_duty_first);
-  uint32_t* thr = (uint32_t*)(h + o_thr);
-  uint32_t* pd = (uint32_t*)(h + o_pduty);
-  // offsets first, then every caller batch packed by its own worker (the
-  // sections are disjoint): a 16-batch group is ~70 MB of host copies, which
-  // one thread would take longer to pack than the GPU takes to run it
-  std::vector<Part> parts(n_batches);
-  std::vector<uint32_t> mb0(n_batches);
+// Batch k's duties / partials / messages follow batch k-1's (mb0: its first
+// message byte); a set launch's one part spans the padded device batch.
+static std::vector<Part> place_parts(const SubmitInput& in, const LaunchDims& d, std::vector<uint32_t>& mb0) {
+  std::vector<Part> parts(in.n_batches);
+  mb0.resize(in.n_batches);
+  const bool verify = d.op != TBG_OP_AGGREGATE;
   uint32_t D = 0, P = 0, M = 0, MB = 0;
-  for (uint32_t k = 0; k < n_batches; ++k) {
-    const tbg_batch* b = bs[k];
+  for (uint32_t k = 0; k < in.n_batches; ++k) {
+    const tbg_batch* b = in.bs[k];
     parts[k].d0 = D;
     parts[k].nd = b->n_duties;
     parts[k].p0 = P;
@@ -1029,89 +699,111 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
     M += parts[k].nm;
     if (verify) MB += b->msg_off[b->n_msgs];
   }
-  auto pack = [&](uint32_t k) {
-    const tbg_batch* b = bs[k];
-    const uint32_t D = parts[k].d0, P = parts[k].p0, M = parts[k].m0, MB = mb0[k];
-    const uint32_t bnd = b->n_duties, bnp = b->n_partials, bnm = parts[k].nm;
-    if (verify) {
-      const uint32_t bmb = b->msg_off[bnm];
-      if (bmb) memcpy(h + o_msgs + MB, b->msgs, bmb);
-      for (uint32_t m = 0; m < bnm; ++m) msg_off[M + m] = MB + b->msg_off[m];
-      for (uint32_t d = 0; d < bnd; ++d) duty_msg[D + d] = M + b->duty_msg[d];
-      if (aggver) memcpy(h + o_pk + 4ull * D, b->pubkey_ids, 4ull * bnd);  // (one group key per duty)
-      else memcpy(h + o_pk + 4ull * P, b->pubkey_ids, 4ull * bnp);
-      if (l0m) {  // this batch's duties by message (sections disjoint from the other batches')
-        std::vector<uint32_t> cursor(bnm);
-        l0m_sort_batch(duty_msg, D, bnd, M, bnm, (uint32_t*)(h + o_mfirst), (uint32_t*)(h + o_mduty), cursor.data());
-      }
+  if (d.sets) parts[0].nd = d.n_duties;
+  return parts;
+}
+
+// One caller batch into its place, every index rebased by the running offsets.
+static void pack_batch(const tbg_batch* b, const Part& q, uint32_t MB, const DevBatch& H, const LaunchPlan& plan) {
+  const uint32_t D = q.d0, P = q.p0, M = q.m0;
+  const uint32_t bnd = b->n_duties, bnp = b->n_partials, bnm = q.nm;
+  uint32_t* msg_off = (uint32_t*)H.msg_off;
+  uint32_t* duty_msg = (uint32_t*)H.duty_msg;
+  uint32_t* duty_first = (uint32_t*)H.duty_first;
+  uint32_t* thr = (uint32_t*)H.duty_threshold;
+  uint32_t* pd = (uint32_t*)H.partial_duty;
+  if (H.op != TBG_OP_AGGREGATE) {
+    const uint32_t bmb = b->msg_off[bnm];
+    if (bmb) memcpy((uint8_t*)H.msgs + MB, b->msgs, bmb);
+    for (uint32_t m = 0; m < bnm; ++m) msg_off[M + m] = MB + b->msg_off[m];
+    for (uint32_t d = 0; d < bnd; ++d) duty_msg[D + d] = M + b->duty_msg[d];
+    if (plan.aggver) memcpy((uint32_t*)H.pubkey_ids + D, b->pubkey_ids, 4ull * bnd);  // (one group key per duty)
+    else memcpy((uint32_t*)H.pubkey_ids + P, b->pubkey_ids, 4ull * bnp);
+    if (plan.l0m) {  // this batch's duties by message (sections disjoint from the other batches')
+      std::vector<uint32_t> cursor(bnm);
+      l0m_sort_batch(duty_msg, D, bnd, M, bnm, (uint32_t*)H.msg_first, (uint32_t*)H.msg_duty, cursor.data());
     }
-    for (uint32_t d = 0; d < bnd; ++d) {
-      duty_first[D + d] = P + b->duty_first[d];
-      for (uint32_t j = b->duty_first[d]; j < b->duty_first[d + 1]; ++j) pd[P + j] = D + d;
+  }
+  for (uint32_t d = 0; d < bnd; ++d) {
+    duty_first[D + d] = P + b->duty_first[d];
+    for (uint32_t j = b->duty_first[d]; j < b->duty_first[d + 1]; ++j) pd[P + j] = D + d;
+  }
+  if (H.op == TBG_OP_VERIFY_AGGREGATE) memcpy(thr + D, b->duty_threshold, 4ull * bnd);
+  else memset(thr + D, 0, 4ull * bnd);
+  if (bnp) {
+    memcpy((uint8_t*)H.sigs + 96ull * P, b->sigs, 96ull * bnp);
+    memcpy((uint8_t*)H.identifiers + P, b->identifiers, bnp);
+  }
+}
+
+// A set launch (one caller batch): the duties move to their padded places,
+// set k's first on a multiple of Gp; a padding duty is empty (no partials,
+// message 0), which k_rlc_duty_sum leaves RLC_NONE.  Partials and messages
+// keep their indices.
+static void pack_sets(const SubmitInput& in, const DevBatch& H, const LaunchPlan& plan) {
+  const tbg_batch* b = in.bs[0];
+  const uint32_t Gp = plan.G ? plan.G : 1;
+  const uint32_t nd = H.n_duties, np = H.n_partials, nm = H.n_msgs;
+  uint32_t* duty_msg = (uint32_t*)H.duty_msg;
+  uint32_t* duty_first = (uint32_t*)H.duty_first;
+  uint32_t* pd = (uint32_t*)H.partial_duty;
+  uint32_t* dset = (uint32_t*)H.duty_set;
+  if (b->msg_off[nm]) memcpy((uint8_t*)H.msgs, b->msgs, b->msg_off[nm]);
+  memcpy((uint32_t*)H.msg_off, b->msg_off, 4ull * nm);
+  if (np) {
+    memcpy((uint32_t*)H.pubkey_ids, b->pubkey_ids, 4ull * np);
+    memcpy((uint8_t*)H.sigs, b->sigs, 96ull * np);
+    memcpy((uint8_t*)H.identifiers, b->identifiers, np);
+  }
+  uint32_t e = 0;
+  for (uint32_t k = 0; k < in.n_sets; ++k) {
+    const uint32_t a = in.set_first[k], z = in.set_first[k + 1];
+    if (a == z) continue;
+    for (; e % Gp; ++e) {
+      duty_first[e] = b->duty_first[a];
+      duty_msg[e] = 0;
+      dset[e] = k;
     }
-    if (op == TBG_OP_VERIFY_AGGREGATE) memcpy(thr + D, b->duty_threshold, 4ull * bnd);
-    else memset(thr + D, 0, 4ull * bnd);
-    if (bnp) {
-      memcpy(h + o_sigs + 96ull * P, b->sigs, 96ull * bnp);
-      memcpy(h + o_ids + P, b->identifiers, bnp);
+    for (uint32_t d = a; d < z; ++d, ++e) {
+      duty_first[e] = b->duty_first[d];
+      duty_msg[e] = b->duty_msg[d];
+      dset[e] = k;
+      for (uint32_t j = b->duty_first[d]; j < b->duty_first[d + 1]; ++j) pd[j] = e;
     }
-  };
-  // A set launch (one caller batch): the duties move to their padded places,
-  // set k's first on a multiple of Gp; a padding duty is empty (no partials,
-  // message 0), which k_rlc_duty_sum leaves RLC_NONE.  Partials and messages
-  // keep their indices.
-  auto pack_sets = [&]() {
-    const tbg_batch* b = bs[0];
-    const uint32_t Gp = G ? G : 1;
-    uint32_t* dset = (uint32_t*)(h + o_dset);
-    if (msg_bytes) memcpy(h + o_msgs, b->msgs, msg_bytes);
-    memcpy(msg_off, b->msg_off, 4ull * nm);
-    if (np) {
-      memcpy(h + o_pk, b->pubkey_ids, 4ull * np);
-      memcpy(h + o_sigs, b->sigs, 96ull * np);
-      memcpy(h + o_ids, b->identifiers, np);
-    }
-    uint32_t e = 0;
-    for (uint32_t k = 0; k < n_sets; ++k) {
-      const uint32_t a = set_first[k], z = set_first[k + 1];
-      if (a == z) continue;
-      for (; e % Gp; ++e) {
-        duty_first[e] = b->duty_first[a];
-        duty_msg[e] = 0;
-        dset[e] = k;
-      }
-      for (uint32_t d = a; d < z; ++d, ++e) {
-        duty_first[e] = b->duty_first[d];
-        duty_msg[e] = b->duty_msg[d];
-        dset[e] = k;
-        for (uint32_t j = b->duty_first[d]; j < b->duty_first[d + 1]; ++j) pd[j] = e;
-      }
-    }
-    memset(thr, 0, 4ull * nd);
-    parts[0].nd = nd;
-    if (l0m) {  // (the padded duties: a padding duty names message 0 and is never combined)
-      std::vector<uint32_t> cursor(nm);
-      l0m_sort_batch(duty_msg, 0, nd, 0, nm, (uint32_t*)(h + o_mfirst), (uint32_t*)(h + o_mduty), cursor.data());
-    }
-  };
-  if (l0m) ((uint32_t*)(h + o_mfirst))[0] = 0;
+  }
+  memset((uint32_t*)H.duty_threshold, 0, 4ull * nd);
+  if (plan.l0m) {  // (the padded duties: a padding duty names message 0 and is never combined)
+    std::vector<uint32_t> cursor(nm);
+    l0m_sort_batch(duty_msg, 0, nd, 0, nm, (uint32_t*)H.msg_first, (uint32_t*)H.msg_duty, cursor.data());
+  }
+}
+
+// The whole input image: every caller batch packed by its own worker (the
+// sections are disjoint: a 16-batch group is ~70 MB of host copies, which one
+// thread would take longer to pack than the GPU takes to run it), the arrays'
+// closing entries, and level 0's chunk plan (parts[k].ch1, .maxch).
+static void pack_input(const SubmitInput& in, std::vector<Part>& parts, const std::vector<uint32_t>& mb0, const DevBatch& H,
+                       const LaunchLayout& L) {
+  const LaunchPlan& plan = L.plan;
+  const uint32_t n_batches = in.n_batches, nd = H.n_duties, np = H.n_partials, nm = H.n_msgs;
+  if (plan.l0m) ((uint32_t*)H.msg_first)[0] = 0;
   const uint32_t workers = (np >= (1u << 16) && n_batches > 1) ? std::min<uint32_t>(n_batches, 8) : 1;
-  if (set_first) {
-    pack_sets();
+  if (in.set_first) {
+    pack_sets(in, H, plan);
   } else if (workers == 1) {
-    for (uint32_t k = 0; k < n_batches; ++k) pack(k);
+    for (uint32_t k = 0; k < n_batches; ++k) pack_batch(in.bs[k], parts[k], mb0[k], H, plan);
   } else {
     std::vector<std::thread> th;
     for (uint32_t w = 0; w < workers; ++w)
       th.emplace_back([&, w] {
-        for (uint32_t k = w; k < n_batches; k += workers) pack(k);
+        for (uint32_t k = w; k < n_batches; k += workers) pack_batch(in.bs[k], parts[k], mb0[k], H, plan);
       });
     for (auto& t : th) t.join();
   }
-  duty_first[nd] = np;
-  if (verify) msg_off[nm] = MB;
-  if (aggver)
-    for (uint32_t d = 0; d <= nd; ++d) ((uint32_t*)(h + o_iota))[d] = d;
+  ((uint32_t*)H.duty_first)[nd] = np;
+  if (H.op != TBG_OP_AGGREGATE) ((uint32_t*)H.msg_off)[nm] = (uint32_t)L.dims.msg_bytes;
+  if (plan.aggver)
+    for (uint32_t d = 0; d <= nd; ++d) ((uint32_t*)H.av_iota)[d] = d;
   // Level 0 by message, the chunk plan (chunk -> message, message -> first
   // chunk; the shape of SumPlan, k_sum.hip).  Invariant: the messages of
   // caller batch j follow those of batch j - 1 and a message never spans
@@ -1119,16 +811,88 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   // rows and chunks all follow batch j - 1's -- the first n_msgs entries of
   // msg_first / chunk_first, with the duties and chunks they cover, are a
   // prefix's own plan (tbg_replay_plan n_parts; Part::ch1, ::maxch).
-  if (l0m) {
+  if (plan.l0m) {
     uint32_t nc = 0, largest = 0;
     for (uint32_t k = 0; k < n_batches; ++k) {
-      const uint32_t big = l0m_chunk_plan((const uint32_t*)(h + o_mfirst), parts[k].m0, parts[k].nm,
-                                          (uint32_t*)(h + o_cfirst), (uint32_t*)(h + o_cmsg), &nc);
+      const uint32_t big = l0m_chunk_plan(H.msg_first, parts[k].m0, parts[k].nm, (uint32_t*)H.l0m_chunk_first,
+                                          (uint32_t*)H.l0m_chunk_msg, &nc);
       largest = std::max(largest, big);
       parts[k].ch1 = nc;
       parts[k].maxch = largest;
     }
   }
+}
+
+// The launch's secret keys: of the RLC scalars, and of the subgroup test's digits.
+static void draw_seeds(tbg_ctx* c, DevBatch& B) {
+  uint64_t k[4];
+  if (c->rlc_seed) {
+    uint64_t z = c->rlc_seed;  // splitmix64: fixed, reproducible scalars (tests only)
+    for (auto& w : k) {
+      z += 0x9E3779B97F4A7C15ull;
+      uint64_t x = z;
+      x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+      x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+      w = x ^ (x >> 31);
+    }
+  } else {
+    std::random_device rd;  // the OS entropy source (getrandom / /dev/urandom)
+    for (auto& w : k) w = ((uint64_t)rd() << 32) ^ rd() ^ (++c->seed_ctr * 0x9E3779B97F4A7C15ull);
+  }
+  for (int j = 0; j < 4; ++j) {
+    B.rlc_seed[2 * j] = (uint32_t)(k[j] >> 32);
+    B.rlc_seed[2 * j + 1] = (uint32_t)k[j];
+  }
+  // The batched subgroup test's key never follows rlc_seed:
+  // its soundness needs coefficients a submitter cannot predict.
+  std::random_device rd;
+  for (auto& w : B.sgb_seed) w = rd() ^ (uint32_t)(++c->seed_ctr * 0x9E3779B9u);
+}
+
+// One H2D copy of the input image, the kernel chain, one D2H copy of the outputs.
+static int enqueue(tbg_ctx* c, Slot* s, const DevBatch& B, const LaunchLayout& L) {
+  hipStream_t st = s->st;
+  // The resident pubkey table may have been (re)loaded on the utility stream
+  // (already complete: tbg_load_pubkeys waits for it; ordered anyway).
+  HIP_TRY(hipStreamWaitEvent(st, c->keys_ready, 0));
+  HIP_TRY(hipMemcpyAsync(s->d_in, s->h_in, L.in_bytes, hipMemcpyHostToDevice, st));
+  const int rc = launch_chain(c, *s, B, s->ev);
+  if (rc != TBG_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(s->h_out, s->d_work + L.w_out, L.out_bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipEventRecord(s->done, st));
+  return TBG_OK;
+}
+
+static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches, tbg_ticket* tickets,
+                       const uint32_t* set_first, uint32_t n_sets) {
+  if (!c || !bs || !tickets || n_batches == 0) return TBG_E_INVALID_ARG;
+  const SubmitInput in{bs, n_batches, set_first, n_sets};
+  LaunchDims d;
+  std::vector<uint32_t> dm;
+  int rc = total_inputs(in, d, dm);
+  if (rc != TBG_OK) return rc;
+  std::unique_lock<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  Slot* s = free_slot(c, d.n_partials);
+  if (!s) return TBG_E_BUSY;
+  const LaunchPlan plan = plan_launch(*c, d, set_first, dm.data(), n_batches);  // (pads d.n_duties for a set launch)
+  c->rlc_group = plan.rlc_group_cfg;
+  if (!plan.ok) return TBG_E_INVALID_ARG;
+  const LaunchLayout L = layout(plan, d);
+  if ((rc = grow_slot(s, L)) != TBG_OK) return rc;
+  // Reserve the slot (busy, its old tickets expired) and pack WITHOUT the
+  // context lock: a 16-batch group is ~70 MB of host copies, during which
+  // other threads' tbg_poll / tbg_collect / tbg_submit must not wait.
+  s->parts.clear();
+  s->busy = true;
+  lk.unlock();
+  const auto t_pack = std::chrono::steady_clock::now();
+  DevBatch H{};
+  memset(&H, 0, sizeof(H));
+  bind(H, L, s->h_in, nullptr);
+  std::vector<uint32_t> mb0;
+  std::vector<Part> parts = place_parts(in, d, mb0);
+  pack_input(in, parts, mb0, H, L);
   const auto t_packed = std::chrono::steady_clock::now();
 
   lk.lock();
@@ -1140,183 +904,20 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   if (hipSetDevice(c->device) != hipSuccess) return release(TBG_E_DEVICE);
   DevBatch B{};
   memset(&B, 0, sizeof(B));
-  B.op = op;
-  B.n_duties = nd;
-  B.n_partials = np;
-  B.n_msgs = nm;
-  uint8_t* di = s->d_in;
-  uint8_t* dw = s->d_work;
-  B.msgs = di + o_msgs;
-  B.msg_off = (const uint32_t*)(di + o_msg_off);
-  B.duty_msg = (const uint32_t*)(di + o_duty_msg);
-  B.duty_first = (const uint32_t*)(di + o_duty_first);
-  B.duty_threshold = (const uint32_t*)(di + o_thr);
-  B.partial_duty = (const uint32_t*)(di + o_pduty);
-  B.sigs = di + o_sigs;
-  B.identifiers = di + o_ids;
-  B.pubkey_ids = (const uint32_t*)(di + o_pk);
-  B.sig_aff = (G2A*)(dw + w_sig_aff);
-  B.h_aff = (G2A*)(dw + w_h_aff);
-  B.h_status = (int32_t*)(dw + w_h_st);
-  B.h_jac = (G2J*)(dw + w_h_jac);
-  B.lam = (uint32_t*)(dw + w_lam);
-  B.sig_lines = (uint32_t*)(dw + w_sl);
-  B.h_lines = (uint32_t*)(dw + w_hl);
-  B.rlc_group = aggver ? 0u : G;  // (the batch itself runs no check: its view does, av_group)
-  {
-    uint64_t k[4];
-    if (c->rlc_seed) {
-      uint64_t z = c->rlc_seed;  // splitmix64: fixed, reproducible scalars (tests only)
-      for (auto& w : k) {
-        z += 0x9E3779B97F4A7C15ull;
-        uint64_t x = z;
-        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-        x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-        w = x ^ (x >> 31);
-      }
-    } else {
-      std::random_device rd;  // the OS entropy source (getrandom / /dev/urandom)
-      for (auto& w : k) w = ((uint64_t)rd() << 32) ^ rd() ^ (++c->seed_ctr * 0x9E3779B97F4A7C15ull);
-    }
-    for (int j = 0; j < 4; ++j) {
-      B.rlc_seed[2 * j] = (uint32_t)(k[j] >> 32);
-      B.rlc_seed[2 * j + 1] = (uint32_t)k[j];
-    }
-    // The batched subgroup test's key never follows rlc_seed:
-    // its soundness needs coefficients a submitter cannot predict.
-    std::random_device rd;
-    for (auto& w : B.sgb_seed) w = rd() ^ (uint32_t)(++c->seed_ctr * 0x9E3779B9u);
-  }
-  B.rlc_chunk = C;
-  B.part_p = (G1J*)(dw + w_pp);
-  B.part_s = (G2J*)(dw + w_ps);
-  B.chunk_f = (uint32_t*)(dw + w_cf);
-  B.chunk_list = (uint32_t*)(dw + w_cl);
-  B.chunk_lines = B.sig_lines;  // (one fallback line buffer, see w_sl)
-  B.dv_p = (G1A*)(dw + w_dvp);
-  B.dv_s = (G2J*)(dw + w_dvs);
-  B.dv_state = (int32_t*)(dw + w_dvst);
-  B.grp_state = (int32_t*)(dw + w_gst);
-  B.grp_lines = (uint32_t*)(dw + w_gl);
-  B.counters = (uint32_t*)(dw + w_cnt);
-  B.part_list = (uint32_t*)(dw + w_pl);
-  B.id_fe = (uint32_t*)(dw + w_dvfe);
-  B.pend_pts = (G2A*)(dw + w_pend);
-  B.chunk_fe = (uint32_t*)(dw + w_cfe);
-  B.cid_list = (uint32_t*)(dw + w_cidl);
-  B.cid_p = (G1A*)(dw + w_cidp);
-  B.cid_lines = B.sig_lines;
-  // Level 1g is opt-in (tbg_config.gident).  Measured
-  // (profiles/r03/gident/): +7 % at 1 % invalid in 20-step runs, whose three
-  // launches reach their latency-bound fallback levels together, but -3 % at
-  // 48 steps and -11 % on config 5, where launches overlap and the
-  // narrowing's shorter lists matter more than its extra levels.
-  B.gident = G > 1 && G <= 64 ? c->gident : 0u;  // (level 1g's lines kernel runs a lane per duty of a group)
-  B.grp_fe = (uint32_t*)(dw + w_gfe);
-  B.gid_list = (uint32_t*)(dw + w_gidl);
-  B.gid_p = (G1A*)(dw + w_gidp);
-  B.gid_lines = B.sig_lines;
-  B.gid_f = (uint32_t*)(dw + w_gidf);
-  B.id_list = (uint32_t*)(dw + w_idl);
-  B.id_p = (G1A*)(dw + w_idp);
-  B.id_lines = B.sig_lines;
-  B.fb_window = fb_w;
-  {
-    // full-grid passes of the duty / partial lists: those the collected
-    // batches' invalid share makes likely (10x margin), every pass for the
-    // per-partial schedule
-    const double share = std::min(1.0, 10.0 * c->invalid_ema);
-    const uint64_t expect = (uint64_t)((double)vp * share);
-    B.fb_full = (G == 0 || fb_w == 0) ? 0xFFFFFFFFu
-                                      : (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (expect / fb_w + 1) * (uint64_t)fb_w);
-  }
-  B.fb_base = 0;
-  B.partial_status = (int32_t*)(dw + w_pst);
-  B.duty_status = (int32_t*)(dw + w_dst);
-  B.agg = dw + w_agg;
-  if (set_first) {
-    B.sets = 1;
-    B.n_sets = n_sets;
-    B.duty_set = (const uint32_t*)(di + o_dset);
-    B.set_status = (int32_t*)(dw + w_sst);
-    B.gident = 0;  // (no level 1g: a failed group is not narrowed)
-  }
-  B.rlc_batch = l0 && !aggver ? 1u : 0u;
-  if (aggver) {
-    B.agg_aff = (G2A*)(dw + w_aaff);
-    B.av_status = (int32_t*)(dw + w_avst);
-    B.av_counters = (uint32_t*)(dw + w_avcnt);
-    B.av_iota = (const uint32_t*)(di + o_iota);
-    B.av_group = G;
-    B.av_chunk = C;
-    B.av_batch = l0 ? 1u : 0u;
-  }
-  B.msm_r = (uint64_t*)(dw + w_mr);
-  B.msm_off = (uint32_t*)(dw + w_moff);
-  B.msm_cur = (uint32_t*)(dw + w_mcur);
-  B.msm_ent = (uint32_t*)(dw + w_ment);
-  B.msm_bkt = (G2J*)(dw + w_mbkt);
-  B.msm_part = (G2J*)(dw + w_mpart);
-  B.msm_sum = (G2J*)(dw + w_msum);
-  B.batch_pt = (G2A*)(dw + w_bpt);
-  B.batch_lines = (uint32_t*)(dw + w_blines);
-  B.batch_f = (uint32_t*)(dw + w_bf);
-  B.grp_f = (uint32_t*)(dw + w_gf);
-  B.gm_off = (uint32_t*)(dw + w_gmoff);
-  B.gm_ent = (uint32_t*)(dw + w_gment);
-  B.gm_part = (G2J*)(dw + w_gmpart);
-  B.gm_lead = (uint32_t*)(dw + w_gmlead);
-  B.gm_list = (uint32_t*)(dw + w_gmlist);
-  B.gm_hist = (uint32_t*)(dw + w_gmhist);
-  B.gm_order = (uint32_t*)(dw + w_gmorder);
-  B.sgb = sgb ? 1u : 0u;
-  B.sgb_m = sgb_m;
-  B.sgb_split = sgb_split;
-  B.sgb_off = (uint32_t*)(dw + w_sgoff);
-  B.sgb_ent = (uint32_t*)(dw + w_sgent);
-  B.sgb_part = (G2J*)(dw + w_sgpart);
-  B.sgb_rank = (uint32_t*)(dw + w_sgrank);
-  B.sgb_code = (uint32_t*)(dw + w_sgcode);
-  B.sgb_bad = (uint32_t*)(dw + w_sgbad);
-  B.sgb_t = (G2J*)(dw + w_sgt);
-  B.l0f_sum = (G2J*)(dw + w_l0fsum);
-  B.l0f_u = (uint32_t*)(dw + w_l0fu);
-  B.l0_duty_partials = c->l0_duty_partials;
-  B.l0_tail_partials = c->l0_tail_partials;
-  B.l0_msg_share = l0m ? c->l0_msg_share : TBG_L0_MSG_NEVER;  // (no plan: never by message)
-  B.l0m_n_chunks = l0m ? parts[n_batches - 1].ch1 : 0;
-  B.l0m_max_chunks = l0m ? parts[n_batches - 1].maxch : 0;
-  B.msg_first = (const uint32_t*)(di + o_mfirst);
-  B.msg_duty = (const uint32_t*)(di + o_mduty);
-  B.l0m_chunk_first = (const uint32_t*)(di + o_cfirst);
-  B.l0m_chunk_msg = (const uint32_t*)(di + o_cmsg);
-  B.l0m_part = (G1J*)(dw + w_l0mpart);
-  B.l0m_cnt = (uint32_t*)(dw + w_l0mcnt);
-  B.l0m_q = (G1A*)(dw + w_l0mq);
-  B.l0m_state = (int32_t*)(dw + w_l0mst);
-  B.agg_acc = (G2J*)(dw + w_aacc);
-  B.agg_list = (uint32_t*)(dw + w_alist);
-
-  hipStream_t st = s->st;
-  // The resident pubkey table may have been (re)loaded on the utility stream
-  // (already complete: tbg_load_pubkeys waits for it; ordered anyway).
-  if (hipStreamWaitEvent(st, c->keys_ready, 0) != hipSuccess ||
-      hipMemcpyAsync(s->d_in, s->h_in, in_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-    return release(TBG_E_DEVICE);
-  rc = launch_chain(c, *s, B, s->ev);
-  if (rc != TBG_OK) return release(rc);
-  if (hipMemcpyAsync(s->h_out, dw + w_out, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipEventRecord(s->done, st) != hipSuccess)
-    return release(TBG_E_DEVICE);
+  bind(B, L, s->d_in, s->d_work);
+  B.l0m_n_chunks = plan.l0m ? parts[n_batches - 1].ch1 : 0;
+  B.l0m_max_chunks = plan.l0m ? parts[n_batches - 1].maxch : 0;
+  draw_seeds(c, B);
+  if ((rc = enqueue(c, s, B, L)) != TBG_OK) return release(rc);
   {
     const auto t_end = std::chrono::steady_clock::now();
     using ns = std::chrono::nanoseconds;
     c->host[0] += 1;
-    c->host[1] += np;
+    c->host[1] += d.n_partials;
     c->host[2] += (uint64_t)std::chrono::duration_cast<ns>(t_packed - t_pack).count();
     c->host[3] += (uint64_t)std::chrono::duration_cast<ns>(t_end - t_packed).count();
   }
-
+  // the slot holds the launch from here on: its parts get their tickets
   for (uint32_t k = 0; k < n_batches; ++k) {
     parts[k].ticket = c->next_ticket++;
     parts[k].pending = true;
@@ -1327,18 +928,9 @@ static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batche
   s->seen_nsub = s->seen_dec = 0;
   s->busy = true;
   s->ticket = s->parts[0].ticket;
-  s->op = op;
-  s->n_duties = nd;
-  s->n_partials = np;
-  s->n_msgs = nm;
-  s->out_bytes = out_bytes;
   s->B = B;
   s->last = B;
-  s->sgb_m_small = sgb_m_small;
-  s->w_out = w_out;
-  s->sets = set_first != nullptr;
-  s->n_sets = set_first ? n_sets : 0;
-  s->o_sets = w_sst - w_out;
+  s->L = L;
   return TBG_OK;
 }
 
@@ -1353,15 +945,21 @@ int tbg_poll(tbg_ctx* c, tbg_ticket t) {
   return q == hipSuccess ? TBG_OK : TBG_E_DEVICE;
 }
 
+// The output sections in the slot's pinned image: derived from h_out and the
+// layout at each use, never kept (a later submit may regrow h_out and fail
+// before it takes the slot over, and the resident batch is still fetched).
+static DevBatch host_outputs(const Slot* s) {
+  DevBatch O{};
+  memset(&O, 0, sizeof(O));
+  bind(O, s->L, nullptr, nullptr, s->h_out);
+  return O;
+}
+
 // A part's slice of the slot's (pinned) output image.
-static void copy_part(const Slot* s, const Part& q, int32_t* pst, int32_t* dst, uint8_t* agg) {
-  const uint32_t np = s->n_partials, nd = s->n_duties;
-  size_t o = 0;
-  auto sec = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 16); return at; };
-  size_t o_pst = sec(4ull * np), o_dst = sec(4ull * nd), o_agg = sec(96ull * nd);
-  if (pst) memcpy(pst, s->h_out + o_pst + 4ull * q.p0, 4ull * q.np);
-  if (dst) memcpy(dst, s->h_out + o_dst + 4ull * q.d0, 4ull * q.nd);
-  if (agg) memcpy(agg, s->h_out + o_agg + 96ull * q.d0, 96ull * q.nd);
+static void copy_part(const DevBatch& O, const Part& q, int32_t* pst, int32_t* dst, uint8_t* agg) {
+  if (pst) memcpy(pst, O.partial_status + q.p0, 4ull * q.np);
+  if (dst) memcpy(dst, O.duty_status + q.d0, 4ull * q.nd);
+  if (agg) memcpy(agg, O.agg + 96ull * q.d0, 96ull * q.nd);
 }
 
 static void part_done(Slot* s, Part* q) {
@@ -1373,9 +971,9 @@ static void part_done(Slot* s, Part* q) {
 
 // A set launch's slice of the output image: the sets' statuses, and the
 // partial statuses (partials keep their caller indices in the padded batch).
-static void copy_sets(const Slot* s, int32_t* sst, int32_t* pst) {
-  if (sst) memcpy(sst, s->h_out + s->o_sets, 4ull * s->n_sets);
-  if (pst) memcpy(pst, s->h_out, 4ull * s->n_partials);  // (partial statuses lead the output image)
+static void copy_sets(const DevBatch& O, int32_t* sst, int32_t* pst) {
+  if (sst) memcpy(sst, O.set_status, 4ull * O.n_sets);
+  if (pst) memcpy(pst, O.partial_status, 4ull * O.n_partials);
 }
 
 // tbg_collect (sets = false) and tbg_collect_sets (sets = true: sst / pst).
@@ -1385,7 +983,7 @@ static int collect_impl(tbg_ctx* c, tbg_ticket t, int32_t* pst, int32_t* dst, ui
   std::unique_lock<std::mutex> lk(c->mu);
   Part* q = nullptr;
   Slot* s = find_ticket(c, t, true, &q);
-  if (!s || q->collecting || s->sets != sets) return TBG_E_TICKET;
+  if (!s || q->collecting || s->L.dims.sets != sets) return TBG_E_TICKET;
   HIP_TRY(hipSetDevice(c->device));
   hipError_t e = hipEventQuery(s->done);
   if (e == hipErrorNotReady) {
@@ -1410,16 +1008,17 @@ static int collect_impl(tbg_ctx* c, tbg_ticket t, int32_t* pst, int32_t* dst, ui
     return TBG_E_DEVICE;
   }
   const auto t_gather = std::chrono::steady_clock::now();
-  if (sets) copy_sets(s, sst, pst);
-  else copy_part(s, *q, pst, dst, agg);
+  const DevBatch O = host_outputs(s);
+  if (sets) copy_sets(O, sst, pst);
+  else copy_part(O, *q, pst, dst, agg);
   if (sets) {
     // every candidate of a failed group counts as invalid: an upper bound of
     // the invalid share, so level 0 switches off under bad sets as it does
     // under bad partials
-    s->seen_bad += (uint32_t)((const int32_t*)(s->h_out + s->o_sets))[s->n_sets + SET_BAD];
+    s->seen_bad += (uint32_t)O.set_status[O.n_sets + SET_BAD];
     s->seen_total += q->np;
-  } else if (s->op == TBG_OP_AGGREGATE_VERIFY) {  // the duties whose aggregate failed, over the duties checked
-    const int32_t* ds = (const int32_t*)(s->h_out + align_up(4ull * s->n_partials, 16));  // (copy_part's layout)
+  } else if (s->L.dims.op == TBG_OP_AGGREGATE_VERIFY) {  // the duties whose aggregate failed, over the duties checked
+    const int32_t* ds = O.duty_status;
     uint32_t bad = 0, checked = 0;
     for (uint32_t d = 0; d < q->nd; ++d) {
       const int32_t v = ds[q->d0 + d];
@@ -1428,15 +1027,15 @@ static int collect_impl(tbg_ctx* c, tbg_ticket t, int32_t* pst, int32_t* dst, ui
     }
     s->seen_bad += bad;
     s->seen_total += checked;
-  } else if (s->op != TBG_OP_AGGREGATE && q->np) {  // the adaptive group size's and level 0's input
-    const int32_t* st = (const int32_t*)s->h_out;  // partial statuses lead the output region
+  } else if (s->L.dims.op != TBG_OP_AGGREGATE && q->np) {  // the adaptive group size's and level 0's input
+    const int32_t* st = O.partial_status;
     uint32_t bad = 0;
     for (uint32_t i = 0; i < q->np; ++i) bad += st[q->p0 + i] == TBG_PS_INVALID ? 1u : 0u;
     s->seen_bad += bad;
     s->seen_total += q->np;
   }
   if (q->np) {  // the batched subgroup test's input: non-subgroup share of all partials
-    const int32_t* st = (const int32_t*)s->h_out;
+    const int32_t* st = O.partial_status;
     uint32_t ns = 0;
     for (uint32_t i = 0; i < q->np; ++i) ns += st[q->p0 + i] == TBG_PS_ERR_SUBGROUP ? 1u : 0u;
     s->seen_nsub += ns;
@@ -1446,7 +1045,7 @@ static int collect_impl(tbg_ctx* c, tbg_ticket t, int32_t* pst, int32_t* dst, ui
   c->host[5] += q->np;
   c->host[6] += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() -
                                                                                t_gather).count();
-  chain_times(s->ev, s->ms, s->op);
+  chain_times(s->ev, s->ms, s->L.dims.op);
   memcpy(c->last_ms, s->ms, sizeof(c->last_ms));
   part_done(s, q);
   // One update per DEVICE batch, over all of its parts (whatever order they
@@ -1499,7 +1098,7 @@ int tbg_replay_plan(tbg_ctx* c, const tbg_ticket* tickets, const uint32_t* n_par
       B.l0m_max_chunks = last.maxch;
       // the subgroup test's schedule follows the prefix's own partials
       if (B.sgb && sgb_triple(B.sgb_m)) {
-        B.sgb_m = sgb_group_size(c, B.n_partials, sl[k]->sgb_m_small, true);
+        B.sgb_m = sgb_group_size(*c, B.n_partials, sl[k]->L.plan.sgb_m_small, true);
         B.sgb_split = sgb_triple(B.sgb_m) ? 1u : sgb_split_for(B.sgb_m);
       }
     }
@@ -1519,7 +1118,7 @@ int tbg_replay_plan(tbg_ctx* c, const tbg_ticket* tickets, const uint32_t* n_par
     uint32_t k1 = k0 + 1;
     while (k1 < n_launches && std::find(sl.begin() + k0, sl.begin() + k1, sl[k1]) == sl.begin() + k1) ++k1;
     // The level-0 launches run together share the SIMDs: their shape follows
-    // their duties together (l0_shape), where each launch's arena fits it.
+    // their duties together (l0_shape), where each launch's arena fits it (shape_fits).
     if (c->chunk_auto && c->rlc_auto) {
       uint64_t nd = 0;
       bool all_l0 = true;
@@ -1532,13 +1131,12 @@ int tbg_replay_plan(tbg_ctx* c, const tbg_ticket* tickets, const uint32_t* n_par
       uint32_t G = 16, C = 4;
       auto fits_all = [&](uint32_t g, uint32_t ch) {
         for (uint32_t k = k0; k < k1; ++k)
-          if (!l0_shape_fits(sl[k]->n_duties, sl[k]->B.rlc_group, sl[k]->B.rlc_chunk, bs[k].n_duties, g, ch))
-            return false;
+          if (!shape_fits(sl[k]->L, bs[k].n_duties, bs[k].n_partials, bs[k].n_msgs, g, ch)) return false;
         return true;
       };
       if (all_l0) l0_shape(nd, c->n_simd, true, G, C, fits_all);
       for (uint32_t k = k0; k < k1 && all_l0; ++k)
-        if (l0_shape_fits(sl[k]->n_duties, sl[k]->B.rlc_group, sl[k]->B.rlc_chunk, bs[k].n_duties, G, C)) {
+        if (shape_fits(sl[k]->L, bs[k].n_duties, bs[k].n_partials, bs[k].n_msgs, G, C)) {
           bs[k].rlc_group = G;
           bs[k].rlc_chunk = C;
         }
@@ -1623,12 +1221,13 @@ static int fetch_impl(tbg_ctx* c, tbg_ticket t, int32_t* pst, int32_t* dst, uint
   std::lock_guard<std::mutex> lk(c->mu);
   Part* q = nullptr;
   Slot* s = find_ticket(c, t, false, &q);
-  if (!s || s->sets != sets) return TBG_E_TICKET;
+  if (!s || s->L.dims.sets != sets) return TBG_E_TICKET;
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemcpyAsync(s->h_out, s->d_work + s->w_out, s->out_bytes, hipMemcpyDeviceToHost, s->st));
+  HIP_TRY(hipMemcpyAsync(s->h_out, s->d_work + s->L.w_out, s->L.out_bytes, hipMemcpyDeviceToHost, s->st));
   HIP_TRY(hipStreamSynchronize(s->st));
-  if (sets) copy_sets(s, sst, pst);
-  else copy_part(s, *q, pst, dst, agg);
+  const DevBatch O = host_outputs(s);
+  if (sets) copy_sets(O, sst, pst);
+  else copy_part(O, *q, pst, dst, agg);
   return TBG_OK;
 }
 
@@ -1648,7 +1247,7 @@ int tbg_fetch_stats(tbg_ctx* c, tbg_ticket t, uint32_t* out4) {
   HIP_TRY(hipSetDevice(c->device));
   uint32_t cnt[CNT_WORDS] = {};
   const DevBatch L = checked_batch(s->last);  // (TBG_OP_AGGREGATE_VERIFY: the aggregates' checks)
-  if (s->op != TBG_OP_AGGREGATE) {
+  if (s->L.dims.op != TBG_OP_AGGREGATE) {
     HIP_TRY(hipMemcpyAsync(cnt, L.counters, sizeof(cnt), hipMemcpyDeviceToHost, s->st));
     HIP_TRY(hipStreamSynchronize(s->st));
   }
@@ -1668,7 +1267,7 @@ int tbg_fetch_fallback(tbg_ctx* c, tbg_ticket t, uint32_t* out8) {
   HIP_TRY(hipSetDevice(c->device));
   uint32_t cnt[CNT_WORDS] = {};
   const DevBatch L = checked_batch(s->last);  // (TBG_OP_AGGREGATE_VERIFY: the aggregates' checks)
-  if (s->op != TBG_OP_AGGREGATE) {
+  if (s->L.dims.op != TBG_OP_AGGREGATE) {
     HIP_TRY(hipMemcpyAsync(cnt, L.counters, sizeof(cnt), hipMemcpyDeviceToHost, s->st));
     HIP_TRY(hipStreamSynchronize(s->st));
   }
@@ -1679,7 +1278,7 @@ int tbg_fetch_fallback(tbg_ctx* c, tbg_ticket t, uint32_t* out8) {
   out8[4] = cnt[CNT_DUTIES];
   out8[5] = cnt[CNT_PARTIALS];
   out8[6] = L.rlc_group;
-  out8[7] = s->op == TBG_OP_AGGREGATE || !L.rlc_batch ? (uint32_t)TBG_L0_NOT_RUN
+  out8[7] = s->L.dims.op == TBG_OP_AGGREGATE || !L.rlc_batch ? (uint32_t)TBG_L0_NOT_RUN
             : cnt[CNT_L0_OK]                              ? (uint32_t)TBG_L0_PASSED
                                                           : (uint32_t)TBG_L0_FAILED;
   return TBG_OK;
@@ -1754,7 +1353,7 @@ int tbg_fetch_level0_msgs(tbg_ctx* c, tbg_ticket t, uint32_t* out2) {
   // (the launch's own fields: launch_rlc_check took its path from the same ones)
   const DevBatch B = checked_batch(s->last);  // (TBG_OP_AGGREGATE_VERIFY: never by message)
   out2[0] = out2[1] = 0;
-  if (s->op == TBG_OP_AGGREGATE || !B.rlc_batch || !B.rlc_group || !B.n_duties) return TBG_OK;
+  if (s->L.dims.op == TBG_OP_AGGREGATE || !B.rlc_batch || !B.rlc_group || !B.n_duties) return TBG_OK;
   const bool by_msg = l0_by_msg(B);
   const uint32_t n = by_msg ? B.n_msgs : B.n_duties;
   out2[0] = by_msg ? 1u : 0u;
@@ -1769,7 +1368,7 @@ int tbg_fetch_level0(tbg_ctx* c, tbg_ticket t, int32_t* state) {
   if (!s) return TBG_E_TICKET;
   *state = TBG_L0_NOT_RUN;
   const DevBatch L = checked_batch(s->last);  // (TBG_OP_AGGREGATE_VERIFY: the aggregates' checks)
-  if (s->op == TBG_OP_AGGREGATE || !L.rlc_batch) return TBG_OK;
+  if (s->L.dims.op == TBG_OP_AGGREGATE || !L.rlc_batch) return TBG_OK;
   HIP_TRY(hipSetDevice(c->device));
   uint32_t cnt[CNT_WORDS] = {};
   HIP_TRY(hipMemcpyAsync(cnt, L.counters, sizeof(cnt), hipMemcpyDeviceToHost, s->st));
@@ -1826,8 +1425,8 @@ int tbg_sign(tbg_ctx* c, const uint8_t* sk32, uint32_t n, const uint8_t* msgs, c
                 align_up(3 * sizeof(G2J) * (size_t)n_msgs, 16);
   uint8_t* base = nullptr;
   if (hipMalloc(&base, need) != hipSuccess) return TBG_E_OOM;
-  size_t o = 0;
-  auto sec = [&](size_t bytes) { uint8_t* p = base + o; o += align_up(bytes, 16); return p; };
+  Arena a;
+  auto sec = [&](size_t bytes) { return base + a.take(bytes); };
   uint8_t* d_sk = sec(32ull * n);
   uint8_t* d_msgs = sec(mb + 1);
   uint32_t* d_off = (uint32_t*)sec(4ull * (n_msgs + 1));
@@ -1901,7 +1500,7 @@ struct KeyedScope {
   uint8_t* d_sk = nullptr;    // [sk_bytes] inside it
   uint8_t* h_sk = nullptr;    // [sk_bytes] pinned (hipHostMalloc)
   size_t sk_bytes = 0;
-  size_t o = 0;
+  Arena arena;
   ~KeyedScope() {
     if (d_sk) (void)hipMemsetAsync(d_sk, 0, sk_bytes, st);
     (void)hipStreamSynchronize(st);
@@ -1911,11 +1510,7 @@ struct KeyedScope {
     }
     if (d_base) (void)hipFree(d_base);
   }
-  uint8_t* sec(size_t bytes) {
-    uint8_t* p = d_base + o;
-    o += align_up(bytes, 16);
-    return p;
-  }
+  uint8_t* sec(size_t bytes) { return d_base + arena.take(bytes); }
   // The workspace and the staging; the keys go into the staging with every
   // rejected one replaced by 1 (masks, no branch on a key byte), their codes into kst.
   int open(hipStream_t stream, size_t work_bytes, const uint8_t* sk32, uint32_t n, std::vector<int32_t>& kst) {
@@ -2042,16 +1637,12 @@ namespace {
 // One device allocation for a utility call, freed on scope exit.
 struct DevArena {
   uint8_t* base = nullptr;
-  size_t o = 0;
+  Arena arena;
   ~DevArena() {
     if (base) hipFree(base);
   }
   int alloc(size_t bytes) { return hipMalloc(&base, bytes ? bytes : 16) == hipSuccess ? TBG_OK : TBG_E_OOM; }
-  uint8_t* sec(size_t bytes) {
-    uint8_t* p = base + o;
-    o += align_up(bytes, 16);
-    return p;
-  }
+  uint8_t* sec(size_t bytes) { return base + arena.take(bytes); }
 };
 
 bool offsets_ok(const uint32_t* off, uint32_t n_sets) {

@@ -259,7 +259,7 @@ constexpr uint32_t MSM_SUM_ENTRIES = 128;
 #define TBG_SGB_SPLIT 4
 #endif
 // The group size follows the non-subgroup share of the collected batches
-// (sgb_plan, tbls_engine.hip): SGB_M while clean, down to SGB_M_MIN when a
+// (sgb_plan, tbls_plan.h): SGB_M while clean, down to SGB_M_MIN when a
 // few signatures per thousand are outside G2 (a failed group costs its
 // members' per-signature tests).
 constexpr uint32_t SGB_M = TBG_SGB_M;  // largest group: consecutive partials (LDS of k_sgb_sort)
@@ -294,7 +294,7 @@ constexpr uint32_t SGB_PRANK = (SGB_PBUCKETS + 31) / 32 * 32;  // k_sgb_bucket's
 // 8.9.  Its reductions cost ~2,400 additions per triple whatever the group's
 // size, so it pays only in groups of many thousands, which no longer fit the
 // sort's LDS: the sort runs in global memory (k_sgb_tri_*).  Only large clean
-// launches take it (sgb_plan, tbls_engine.hip; tbg_config.sgb_tri_partials,
+// launches take it (sgb_plan, tbls_plan.h; tbg_config.sgb_tri_partials,
 // sgb_tri_m); every group of at most SGB_M keeps the schedules above.
 #ifndef TBG_SGB_TRI_M
 #define TBG_SGB_TRI_M 16384
@@ -466,7 +466,7 @@ TBG_HD bool participates(uint32_t op, int32_t st) {
 // never the identity (TBG_DS_AGG_IDENTITY is decided in the recombination), so the view
 // runs no decode and no subgroup test: sgb = 0, hence the classic level 0 (bucket MSM) and
 // no by-message merge, which both need the subgroup test's digits.  It shares the batch's
-// messages, H(m) and RLC work arrays (sized by duties in submit_impl: the batch itself runs
+// messages, H(m) and RLC work arrays (sized by duties in tbls_plan.h's section table: the batch itself runs
 // no check) and owns partial_status and counters.  Derived from the batch's own fields
 // alone: a replayed prefix's view is the prefix's.
 inline DevBatch aggver_view(const DevBatch& B) {

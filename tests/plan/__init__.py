@@ -1,0 +1,60 @@
+"""Host (CPU) build of the launch plan and the arena section table
+(charon_amd/csrc/tbls_plan.h), for tests/test_plan_host.py.
+
+TEST TOOLING ONLY -- see plan_host.cpp.  Built on demand with the ROCm clang
+(host target); the header makes no HIP runtime call, it only reads the HIP
+headers' types.
+"""
+import ctypes
+import os
+import subprocess
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SRC = os.path.join(HERE, "plan_host.cpp")
+LIB = os.path.join(HERE, "libplan_host.so")
+CSRC = os.path.join(os.path.dirname(os.path.dirname(HERE)), "charon_amd", "csrc")
+
+
+def _stale():
+    if not os.path.exists(LIB):
+        return True
+    t = os.path.getmtime(LIB)
+    deps = [SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def build():
+    if _stale():
+        rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+        cxx = os.path.join(rocm, "llvm", "bin", "clang++")
+        if not os.path.exists(cxx):
+            cxx = "clang++"
+        tmp = LIB + ".%d.tmp" % os.getpid()
+        subprocess.check_call([cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__",
+                               "-I" + os.path.join(rocm, "include"), "-Wno-pass-failed", SRC, "-o", tmp])
+        os.replace(tmp, LIB)
+    return LIB
+
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        h = ctypes.CDLL(build())
+        p, i, u, q, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double
+        h.pl_max_sections.restype = u
+        h.pl_max_sections.argtypes = []
+        h.pl_layout.restype = i
+        h.pl_layout.argtypes = [p, u, q, p, u, p, u, p, p, p, p]
+        h.pl_bind.restype = i
+        h.pl_bind.argtypes = [p, u, q, p, u, p, u, q, q, q, p, p, p]
+        h.pl_shape_fits.restype = i
+        h.pl_shape_fits.argtypes = [u, u, u, u, u, u]
+        h.pl_l0_shape.restype = None
+        h.pl_l0_shape.argtypes = [q, u, i, u, u, u, u, p, u, p]
+        h.pl_sgb_plan.restype = i
+        h.pl_sgb_plan.argtypes = [d, p]
+        _lib = h
+    return _lib

@@ -1,0 +1,151 @@
+// TEST TOOLING ONLY: C entry points over charon_amd/csrc/tbls_plan.h -- the
+// launch plan, the section layout, bind over fake base addresses and the
+// replay fit rule -- for tests/test_plan_host.py.  Plain host C++: the header
+// makes no HIP runtime call.
+#include <cstdint>
+#include <cstring>
+#include <vector>
+#include "../../charon_amd/csrc/tbls_plan.h"
+
+using namespace tbg;
+
+namespace {
+
+// cfg16: PlanConfig's fields in their order
+PlanConfig config(const double* v) {
+  PlanConfig c;
+  c.rlc_group = (uint32_t)v[0];
+  c.rlc_chunk = (uint32_t)v[1];
+  c.chunk_auto = v[2] != 0;
+  c.rlc_auto = v[3] != 0;
+  c.rlc_batch = (uint32_t)v[4];
+  c.invalid_ema = v[5];
+  c.nonsub_ema = v[6];
+  c.gident = (uint32_t)v[7];
+  c.fb_window = (uint32_t)v[8];
+  c.sgb_mode = (uint32_t)v[9];
+  c.l0_duty_partials = (uint32_t)v[10];
+  c.l0_tail_partials = (uint32_t)v[11];
+  c.l0_msg_share = (uint32_t)v[12];
+  c.sgb_tri_partials = (uint32_t)v[13];
+  c.sgb_tri_m = (uint32_t)v[14];
+  c.n_simd = (uint32_t)v[15];
+  return c;
+}
+
+// batches: [n][3] duties, partials, messages of each caller batch
+bool plan_of(const PlanConfig& c, uint32_t op, uint64_t msg_bytes, const uint32_t* batches, uint32_t n_batches,
+             const uint32_t* set_first, uint32_t n_sets, LaunchLayout& L) {
+  LaunchDims d;
+  d.op = op;
+  d.msg_bytes = (size_t)msg_bytes;
+  d.sets = set_first != nullptr;
+  d.n_sets = n_sets;
+  std::vector<uint32_t> dm(2 * (size_t)n_batches);
+  for (uint32_t k = 0; k < n_batches; ++k) {
+    d.n_duties += batches[3 * k];
+    d.n_partials += batches[3 * k + 1];
+    d.n_msgs += batches[3 * k + 2];
+    dm[2 * k] = batches[3 * k];
+    dm[2 * k + 1] = batches[3 * k + 2];
+  }
+  const LaunchPlan p = plan_launch(c, d, set_first, dm.data(), n_batches);
+  if (!p.ok) return false;
+  L = layout(p, d);
+  return true;
+}
+
+// A slot sized for nd0 duties of three partials, one message each, at a configured (G0, C0), level 0 on.
+LaunchLayout slot_of(uint32_t nd0, uint32_t G0, uint32_t C0) {
+  PlanConfig c;
+  c.rlc_group = G0;
+  c.rlc_chunk = C0;
+  c.chunk_auto = false;
+  c.rlc_batch = TBG_RLC_L0_ON;
+  const uint32_t b[3] = {nd0, 3 * nd0, nd0};
+  LaunchLayout L;
+  plan_of(c, TBG_OP_VERIFY_AGGREGATE, 32ull * nd0, b, 1, nullptr, 0, L);
+  return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t pl_max_sections() { return kMaxSections; }
+
+// plan_out[20]: n_duties, rlc_group_cfg, G, C, l0, vp, fb_w, fb_full, sgb, sgb_m, sgb_m_small, sgb_split, fused, msm,
+// l0m_in, l0m, l0m_chunks, gident, aggver, l0_msg_share; totals[4]: in_bytes, work_bytes, w_out, out_bytes;
+// secs[n][3]: arena, offset, bytes; names[n].  Returns the section count, -1 for a refused plan.
+int pl_layout(const double* cfg16, uint32_t op, uint64_t msg_bytes, const uint32_t* batches, uint32_t n_batches,
+              const uint32_t* set_first, uint32_t n_sets, uint64_t* plan_out, uint64_t* totals, uint64_t* secs,
+              const char** names) {
+  LaunchLayout L;
+  if (!plan_of(config(cfg16), op, msg_bytes, batches, n_batches, set_first, n_sets, L)) return -1;
+  const LaunchPlan& p = L.plan;
+  const uint64_t po[20] = {L.dims.n_duties, p.rlc_group_cfg, p.G, p.C, p.l0, p.vp, p.fb_w, p.fb_full, p.sgb, p.sgb_m,
+                           p.sgb_m_small, p.sgb_split, p.fused, p.msm, p.l0m_in, p.l0m, p.l0m_chunks, p.gident, p.aggver,
+                           p.l0_msg_share};
+  memcpy(plan_out, po, sizeof(po));
+  totals[0] = L.in_bytes;
+  totals[1] = L.work_bytes;
+  totals[2] = L.w_out;
+  totals[3] = L.out_bytes;
+  for (uint32_t i = 0; i < L.n; ++i) {
+    secs[3 * i] = L.sec[i].arena;
+    secs[3 * i + 1] = L.sec[i].off;
+    secs[3 * i + 2] = L.sec[i].bytes;
+    names[i] = L.sec[i].name;
+  }
+  return (int)L.n;
+}
+
+// bind over fake bases (0: that arena is not bound; out_base: the output image apart from the work
+// arena, 0 for its tail): ptrs[n] the members' values in table order, alias[5] sig_lines and its four
+// aliases, scalars[12]: op, n_duties, n_partials, n_msgs, rlc_group, rlc_chunk, rlc_batch, fb_window, sgb, sgb_m,
+// sets, n_sets
+int pl_bind(const double* cfg16, uint32_t op, uint64_t msg_bytes, const uint32_t* batches, uint32_t n_batches,
+            const uint32_t* set_first, uint32_t n_sets, uint64_t in_base, uint64_t work_base, uint64_t out_base, uint64_t* ptrs,
+            uint64_t* alias, uint32_t* scalars) {
+  LaunchLayout L;
+  if (!plan_of(config(cfg16), op, msg_bytes, batches, n_batches, set_first, n_sets, L)) return -1;
+  DevBatch B;
+  memset(&B, 0, sizeof(B));
+  bind(B, L, (uint8_t*)(uintptr_t)in_base, (uint8_t*)(uintptr_t)work_base, (uint8_t*)(uintptr_t)out_base);
+  uint32_t i = 0;
+  for_each_section(L.plan, L.dims,
+                   [&](const char*, auto member, ArenaId, size_t, bool) { ptrs[i++] = (uint64_t)(uintptr_t)(B.*member); });
+  const void* al[5] = {B.sig_lines, B.chunk_lines, B.cid_lines, B.gid_lines, B.id_lines};
+  for (int k = 0; k < 5; ++k) alias[k] = (uint64_t)(uintptr_t)al[k];
+  const uint32_t sc[12] = {B.op, B.n_duties, B.n_partials, B.n_msgs, B.rlc_group, B.rlc_chunk, B.rlc_batch, B.fb_window,
+                           B.sgb, B.sgb_m, B.sets, B.n_sets};
+  memcpy(scalars, sc, sizeof(sc));
+  return (int)L.n;
+}
+
+// The fit rule derived from the table: nd duties at (G, C) in a slot laid out for nd0 duties at (G0, C0).
+int pl_shape_fits(uint32_t nd0, uint32_t G0, uint32_t C0, uint32_t nd, uint32_t G, uint32_t C) {
+  return shape_fits(slot_of(nd0, G0, C0), nd, 3 * nd, nd, G, C) ? 1 : 0;
+}
+
+// l0_shape; with n_prefix > 0 under the filter "every prefix_nd[k] fits a slot of (nd0, G0, C0)"
+void pl_l0_shape(uint64_t nd, uint32_t n_simd, int g_free, uint32_t G, uint32_t nd0, uint32_t G0, uint32_t C0,
+                 const uint32_t* prefix_nd, uint32_t n_prefix, uint32_t* out_gc) {
+  uint32_t C = 0;
+  if (n_prefix) {
+    const LaunchLayout slot = slot_of(nd0, G0, C0);
+    l0_shape(nd, n_simd, g_free != 0, G, C, [&](uint32_t g, uint32_t ch) {
+      for (uint32_t k = 0; k < n_prefix; ++k)
+        if (!shape_fits(slot, prefix_nd[k], 3 * prefix_nd[k], prefix_nd[k], g, ch)) return false;
+      return true;
+    });
+  } else {
+    l0_shape(nd, n_simd, g_free != 0, G, C, l0_fits_any);
+  }
+  out_gc[0] = G;
+  out_gc[1] = C;
+}
+
+int pl_sgb_plan(double rho, uint32_t* m) { return sgb_plan(rho, *m) ? 1 : 0; }
+
+}  // extern "C"

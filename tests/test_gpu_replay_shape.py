@@ -1,5 +1,5 @@
 """tbg_replay_plan with the level-0 shape of the launches it runs together
-(tbls_engine.hip: l0_shape over their duties, applied where each slot's
+(tbls_engine.hip tbg_replay_plan: l0_shape over their duties, applied where each slot's
 arena fits it).  Three slots of 16 caller batches of 2,500 3-of-4 DVs
 (40k duties each, submitted at (G, C) = (16, 4)) replayed as the bench's
 prefixes of 7 + 7 + 6 batches: 50k duties together take the cheapest shape
@@ -22,7 +22,7 @@ PREFIX = [7, 7, 6]
 
 def test_replay_plan_reshaped_launches():
     from charon_amd import engine as eng
-    from tests.test_gpu_shape import expected_shape, shape_fits
+    from tests.plan_mirror import expected_shape, shape_fits
     from tools.workload import make_batch
     n_cu = eng.device_cu_count(0)
     assert expected_shape(DVS * PER_SLOT, n_cu) == (16, 4)
@@ -72,7 +72,7 @@ def test_replay_prefix_keeps_shape_its_chunk_arena_cannot_hold():
     group fails level 0 and level 1, so the chunk-level kernels write every
     chunk slot: the prefix must still equal its known answer."""
     from charon_amd import engine as eng
-    from tests.test_gpu_shape import expected_shape, shape_fits
+    from tests.plan_mirror import expected_shape, shape_fits
     from tools.workload import make_batch
     n_cu = eng.device_cu_count(0)
     assert expected_shape(160000, n_cu) == (16, 8)

@@ -16,6 +16,8 @@ import os
 import numpy as np
 import pytest
 
+from tests.plan_mirror import sgb_plan
+
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -80,18 +82,6 @@ def test_crafted_points_match_oracle_batched_and_alone(engines):
     assert sg2["groups"] == 0
     assert np.array_equal(res2.partial_status, res.partial_status)
     assert np.array_equal(res2.duty_status, res.duty_status) and np.array_equal(res2.agg, res.agg)
-
-
-def sgb_plan(rho):
-    """Mirror of tbls_engine.hip sgb_plan: (on, partials per group)."""
-    best, m = None, None
-    k = M
-    while k >= 64:
-        cost = 0.55 + 1.1 * 18 / k + 1 - (1 - min(rho, 1.0)) ** k
-        if best is None or cost < best - 1e-12:
-            best, m = cost, k
-        k //= 2
-    return best < 0.95, m
 
 
 def test_adaptive_mode_group_size_and_off(engines):

@@ -16,6 +16,8 @@ import os
 import numpy as np
 import pytest
 
+from tests.plan_mirror import sgb_plan
+
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -169,17 +171,6 @@ def test_a_negated_signature_gives_the_same_verdicts_as_alone(ctx):
         assert np.array_equal(res.duty_status, res_off.duty_status) and np.array_equal(res.agg, res_off.agg)
     finally:
         e.close()
-
-
-def sgb_plan(rho):
-    """Mirror of tbls_engine.hip sgb_plan: (on, partials per group)."""
-    best, m, k = None, None, M
-    while k >= 64:
-        cost = 0.55 + 1.1 * 18 / k + 1 - (1 - min(rho, 1.0)) ** k
-        if best is None or cost < best - 1e-12:
-            best, m = cost, k
-        k //= 2
-    return best < 0.95, m
 
 
 def test_groups_below_the_threshold_keep_the_classic_schedule(ctx):

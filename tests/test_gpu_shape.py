@@ -1,4 +1,4 @@
-"""The level-0 launch shape (tbls_engine.hip l0_shape):
+"""The level-0 launch shape (tbls_plan.h l0_shape):
 a level-0 launch whose Miller hexads at (G, C) = (16, 4) need more than one
 round of the device's wave slots takes the (G, C) with the fewest rounds x
 hexad length (round 6: one-chunk groups of 5 .. 10 duties among the
@@ -9,43 +9,12 @@ import numpy as np
 import pytest
 
 from tests.conftest import progress
+from tests.plan_mirror import expected_shape, shape_fits
 from tests.test_gpu_fullsize import assert_same, oracle_run
 from tests.test_gpu_headline import _call, _known_answer
 
 pytestmark = pytest.mark.gpu
 DVS = 125000
-
-
-def shape_fits(nd0, G0, C0, nd, G, C):
-    """Mirror of l0_shape_fits: a launch of nd duties at (G, C) in an arena
-    sized for nd0 duties at (G0, C0)."""
-    ng0, nch0 = -(-nd0 // G0), -(-G0 // C0)
-    ng, nch = -(-nd // G), -(-G // C)
-    return (ng <= ng0 and ng * (nch + 1) <= ng0 * (nch0 + 1) and ng * nch <= ng0 * nch0
-            and ng * nch * C <= ng0 * nch0 * C0 and ng * G <= ng0 * G0
-            and max(ng * nch, nd) <= max(ng0 * nch0, nd0) and (G <= 64) == (G0 <= 64))
-
-
-def expected_shape(nd, n_cu, g_free=True, G=16, fits=lambda g, c: True):
-    """Mirror of l0_shape: the hexad cost 0.948 + 1.395 C (M u32 mul-adds,
-    profiles/work_model.json) x ceil(waves / SIMDs), SIMDs = CUs x 4, over the
-    candidates `fits` keeps (a replay's arenas)."""
-    n_simd = n_cu * 4
-
-    def cost(g, c):
-        waves = -(-(-(-nd // g) * -(-g // c)) // 10)
-        return (0.948 + 1.395 * c) * -(-waves // n_simd)
-
-    if G < 8:
-        return G, 4
-    cand = [(16 if g_free else G, 4), (16 if g_free else G, 8)] + ([(14, 7)] if g_free else [])
-    if g_free:
-        cand += [(c, c) for c in range(5, 11)]  # round 6: one chunk per group, 5 .. 10 duties
-    best = None
-    for gc in cand:
-        if fits(*gc) and (best is None or cost(*gc) < cost(*best) - 1e-9):
-            best = gc
-    return best
 
 
 def test_shape_mirror():

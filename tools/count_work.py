@@ -107,7 +107,7 @@ def main():
     nch = G // C
     # a P-chunk hexad of c duties costs base + c * per_duty (62 squarings, 68
     # line products per duty): the level-0 launch shape (G, C) varies with the
-    # launch size (tbls_engine.hip l0_shape), so the kernels' models are per
+    # launch size (tbls_plan.h l0_shape), so the kernels' models are per
     # chunk and per duty
     chunk8, _ = measure(lib.hc_stage_miller_chunk, 8, 0)
     chunk_per_duty = (chunk8 - chunk2) / 4
