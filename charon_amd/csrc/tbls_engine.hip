@@ -21,6 +21,7 @@
 #include <vector>
 #include "tbls_launch.h"
 #include "tbls_plan.h"
+#include "tbls_work.h"
 #include "bls_l0msg.h"
 #include "bls_lines.h"
 
@@ -552,6 +553,14 @@ static void chain_times(hipEvent_t* e, float* ms, uint32_t op) {
   hipEventElapsedTime(&ms[7], e[0], e[chain_end(op)]);
 }
 
+// n + 1 offsets of n consecutive ranges: from 0, non-decreasing.
+static bool offsets_ok(const uint32_t* off, uint32_t n) {
+  if (!off || off[0] != 0) return false;
+  for (uint32_t s = 0; s < n; ++s)
+    if (off[s + 1] < off[s]) return false;
+  return true;
+}
+
 static int validate(const tbg_batch* b) {
   if (!b) return TBG_E_INVALID_ARG;
   if (b->op < TBG_OP_VERIFY || b->op > TBG_OP_AGGREGATE_VERIFY) return TBG_E_INVALID_ARG;
@@ -565,10 +574,7 @@ static int validate(const tbg_batch* b) {
   if (b->op != TBG_OP_AGGREGATE) {
     // (pubkey_ids: [n_partials]; under TBG_OP_AGGREGATE_VERIFY [n_duties], one group key per
     // duty -- required either way; duty_threshold is not read under that op)
-    if (!b->msg_off || !b->duty_msg || !b->pubkey_ids || b->n_msgs == 0) return TBG_E_INVALID_ARG;
-    if (b->msg_off[0] != 0) return TBG_E_INVALID_ARG;
-    for (uint32_t m = 0; m < b->n_msgs; ++m)
-      if (b->msg_off[m + 1] < b->msg_off[m]) return TBG_E_INVALID_ARG;
+    if (!b->duty_msg || !b->pubkey_ids || b->n_msgs == 0 || !offsets_ok(b->msg_off, b->n_msgs)) return TBG_E_INVALID_ARG;
     if (b->msg_off[b->n_msgs] && !b->msgs) return TBG_E_INVALID_ARG;
     for (uint32_t d = 0; d < b->n_duties; ++d)
       if (b->duty_msg[d] >= b->n_msgs) return TBG_E_INVALID_ARG;
@@ -587,6 +593,26 @@ static Slot* find_ticket(tbg_ctx* c, tbg_ticket t, bool want_pending, Part** par
         return &x;
       }
   return nullptr;
+}
+
+// A collected ticket's slot for the reads below: the context's lock held while
+// this lives, the slot found (rc TBG_E_TICKET otherwise) and the device set.
+struct Collected {
+  std::lock_guard<std::mutex> lk;
+  Slot* s;
+  int rc;
+  Collected(tbg_ctx* c, tbg_ticket t) : lk(c->mu), s(find_ticket(c, t, false, nullptr)) {
+    rc = !s ? TBG_E_TICKET : hipSetDevice(c->device) != hipSuccess ? TBG_E_DEVICE : TBG_OK;
+  }
+};
+
+// The counters of the checks that B (the slot's last run) made; zeros after TBG_OP_AGGREGATE, which makes none.
+static int read_counters(const Slot* s, const DevBatch& B, uint32_t (&cnt)[CNT_WORDS]) {
+  memset(cnt, 0, sizeof(cnt));
+  if (s->L.dims.op == TBG_OP_AGGREGATE) return TBG_OK;
+  HIP_TRY(hipMemcpyAsync(cnt, B.counters, sizeof(cnt), hipMemcpyDeviceToHost, s->st));
+  HIP_TRY(hipStreamSynchronize(s->st));
+  return TBG_OK;
 }
 
 static int submit_impl(tbg_ctx* c, const tbg_batch* const* bs, uint32_t n_batches, tbg_ticket* tickets,
@@ -1241,16 +1267,12 @@ int tbg_fetch_sets(tbg_ctx* c, tbg_ticket t, int32_t* set_status, int32_t* parti
 
 int tbg_fetch_stats(tbg_ctx* c, tbg_ticket t, uint32_t* out4) {
   if (!c || !out4) return TBG_E_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  Slot* s = find_ticket(c, t, false, nullptr);
-  if (!s) return TBG_E_TICKET;
-  HIP_TRY(hipSetDevice(c->device));
-  uint32_t cnt[CNT_WORDS] = {};
+  Collected k(c, t);
+  if (k.rc != TBG_OK) return k.rc;
+  Slot* s = k.s;
   const DevBatch L = checked_batch(s->last);  // (TBG_OP_AGGREGATE_VERIFY: the aggregates' checks)
-  if (s->L.dims.op != TBG_OP_AGGREGATE) {
-    HIP_TRY(hipMemcpyAsync(cnt, L.counters, sizeof(cnt), hipMemcpyDeviceToHost, s->st));
-    HIP_TRY(hipStreamSynchronize(s->st));
-  }
+  uint32_t cnt[CNT_WORDS];
+  if (read_counters(s, L, cnt) != TBG_OK) return TBG_E_DEVICE;
   uint32_t ng = L.rlc_group ? (L.n_duties + L.rlc_group - 1) / L.rlc_group : 0;
   out4[0] = ng;
   out4[1] = cnt[CNT_DUTIES];
@@ -1261,16 +1283,12 @@ int tbg_fetch_stats(tbg_ctx* c, tbg_ticket t, uint32_t* out4) {
 
 int tbg_fetch_fallback(tbg_ctx* c, tbg_ticket t, uint32_t* out8) {
   if (!c || !out8) return TBG_E_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  Slot* s = find_ticket(c, t, false, nullptr);
-  if (!s) return TBG_E_TICKET;
-  HIP_TRY(hipSetDevice(c->device));
-  uint32_t cnt[CNT_WORDS] = {};
+  Collected k(c, t);
+  if (k.rc != TBG_OK) return k.rc;
+  Slot* s = k.s;
   const DevBatch L = checked_batch(s->last);  // (TBG_OP_AGGREGATE_VERIFY: the aggregates' checks)
-  if (s->L.dims.op != TBG_OP_AGGREGATE) {
-    HIP_TRY(hipMemcpyAsync(cnt, L.counters, sizeof(cnt), hipMemcpyDeviceToHost, s->st));
-    HIP_TRY(hipStreamSynchronize(s->st));
-  }
+  uint32_t cnt[CNT_WORDS];
+  if (read_counters(s, L, cnt) != TBG_OK) return TBG_E_DEVICE;
   out8[0] = L.rlc_group ? (L.n_duties + L.rlc_group - 1) / L.rlc_group : 0;
   out8[1] = cnt[CNT_GID];
   out8[2] = cnt[CNT_CHUNKS];
@@ -1286,9 +1304,9 @@ int tbg_fetch_fallback(tbg_ctx* c, tbg_ticket t, uint32_t* out8) {
 
 int tbg_fetch_shape(tbg_ctx* c, tbg_ticket t, uint32_t* out4) {
   if (!c || !out4) return TBG_E_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  Slot* s = find_ticket(c, t, false, nullptr);
-  if (!s) return TBG_E_TICKET;
+  Collected k(c, t);
+  if (k.rc != TBG_OK) return k.rc;
+  Slot* s = k.s;
   const DevBatch L = checked_batch(s->last);  // (TBG_OP_AGGREGATE_VERIFY: the aggregates' checks)
   const uint32_t G = L.rlc_group, C = L.rlc_chunk;
   out4[0] = G;
@@ -1300,10 +1318,9 @@ int tbg_fetch_shape(tbg_ctx* c, tbg_ticket t, uint32_t* out4) {
 
 int tbg_fetch_subgroup(tbg_ctx* c, tbg_ticket t, uint32_t* out3) {
   if (!c || !out3) return TBG_E_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  Slot* s = find_ticket(c, t, false, nullptr);
-  if (!s) return TBG_E_TICKET;
-  HIP_TRY(hipSetDevice(c->device));
+  Collected k(c, t);
+  if (k.rc != TBG_OK) return k.rc;
+  Slot* s = k.s;
   out3[0] = out3[1] = out3[2] = 0;
   if (!s->last.sgb) return TBG_OK;
   out3[2] = s->last.sgb_m;
@@ -1318,9 +1335,9 @@ int tbg_fetch_subgroup(tbg_ctx* c, tbg_ticket t, uint32_t* out3) {
 
 int tbg_fetch_subgroup_schedule(tbg_ctx* c, tbg_ticket t, uint32_t* out1) {
   if (!c || !out1) return TBG_E_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  Slot* s = find_ticket(c, t, false, nullptr);
-  if (!s) return TBG_E_TICKET;
+  Collected k(c, t);
+  if (k.rc != TBG_OK) return k.rc;
+  Slot* s = k.s;
   // (the launch's own fields: the kernels took their schedule from the same ones)
   *out1 = !s->last.sgb                 ? (uint32_t)TBG_SGB_SCHED_NONE
           : sgb_triple(s->last.sgb_m) ? (uint32_t)TBG_SGB_SCHED_TRIPLE
@@ -1337,9 +1354,9 @@ int tbg_host_stats(tbg_ctx* c, uint64_t* out8, int reset) {
 
 int tbg_slot_bytes(tbg_ctx* c, tbg_ticket t, uint64_t* device_bytes, uint64_t* pinned_bytes) {
   if (!c || !device_bytes || !pinned_bytes) return TBG_E_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  Slot* s = find_ticket(c, t, false, nullptr);
-  if (!s) return TBG_E_TICKET;
+  Collected k(c, t);
+  if (k.rc != TBG_OK) return k.rc;
+  Slot* s = k.s;
   *device_bytes = (uint64_t)s->d_in_cap + (uint64_t)s->d_work_cap;
   *pinned_bytes = (uint64_t)s->h_in_cap + (uint64_t)s->h_out_cap;
   return TBG_OK;
@@ -1347,9 +1364,9 @@ int tbg_slot_bytes(tbg_ctx* c, tbg_ticket t, uint64_t* device_bytes, uint64_t* p
 
 int tbg_fetch_level0_msgs(tbg_ctx* c, tbg_ticket t, uint32_t* out2) {
   if (!c || !out2) return TBG_E_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  Slot* s = find_ticket(c, t, false, nullptr);
-  if (!s) return TBG_E_TICKET;
+  Collected k(c, t);
+  if (k.rc != TBG_OK) return k.rc;
+  Slot* s = k.s;
   // (the launch's own fields: launch_rlc_check took its path from the same ones)
   const DevBatch B = checked_batch(s->last);  // (TBG_OP_AGGREGATE_VERIFY: never by message)
   out2[0] = out2[1] = 0;
@@ -1363,16 +1380,14 @@ int tbg_fetch_level0_msgs(tbg_ctx* c, tbg_ticket t, uint32_t* out2) {
 
 int tbg_fetch_level0(tbg_ctx* c, tbg_ticket t, int32_t* state) {
   if (!c || !state) return TBG_E_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  Slot* s = find_ticket(c, t, false, nullptr);
-  if (!s) return TBG_E_TICKET;
+  Collected k(c, t);
+  if (k.rc != TBG_OK) return k.rc;
+  Slot* s = k.s;
   *state = TBG_L0_NOT_RUN;
   const DevBatch L = checked_batch(s->last);  // (TBG_OP_AGGREGATE_VERIFY: the aggregates' checks)
   if (s->L.dims.op == TBG_OP_AGGREGATE || !L.rlc_batch) return TBG_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  uint32_t cnt[CNT_WORDS] = {};
-  HIP_TRY(hipMemcpyAsync(cnt, L.counters, sizeof(cnt), hipMemcpyDeviceToHost, s->st));
-  HIP_TRY(hipStreamSynchronize(s->st));
+  uint32_t cnt[CNT_WORDS];
+  if (read_counters(s, L, cnt) != TBG_OK) return TBG_E_DEVICE;
   *state = cnt[CNT_L0_OK] ? TBG_L0_PASSED : TBG_L0_FAILED;
   return TBG_OK;
 }
@@ -1385,6 +1400,63 @@ int tbg_last_timings(const tbg_ctx* c, float* ms8) {
 
 }  // extern "C"
 
+// ---- the calls that run to completion inside themselves ----------------------
+// Each describes its workspace once (tbls_work.h), owns it through one scope
+// and, once it has enqueued anything, leaves only through that scope.
+namespace {
+
+// The single device allocation of one such call.  Whatever way the call ends,
+// the call's stream is drained first -- copies out of the call's own host
+// vectors may still be queued -- and the memory freed after.
+struct CallScope {
+  hipStream_t st;
+  uint8_t* d_base = nullptr;
+  explicit CallScope(hipStream_t stream) : st(stream) {}
+  CallScope(const CallScope&) = delete;
+  ~CallScope() {
+    (void)hipStreamSynchronize(st);
+    if (d_base) (void)hipFree(d_base);
+  }
+  // Sizes w's workspace by one walk of its sections, allocates, binds w's pointers by a second.
+  template <class W>
+  int open(W& w) {
+    const WorkWalk sized = work_size(w);
+    if (hipMalloc(&d_base, sized.bytes()) != hipSuccess) {
+      d_base = nullptr;
+      return TBG_E_OOM;
+    }
+    work_bind(w, sized, d_base);
+    return TBG_OK;
+  }
+  // The call's return code once its outputs have arrived: rc, or TBG_E_DEVICE if the stream failed.
+  int drain(int rc) { return hipStreamSynchronize(st) != hipSuccess ? TBG_E_DEVICE : rc; }
+};
+
+// A signer's messages, their offsets and the items' message indices, into its workspace.
+int upload_sign_inputs(const SignWork& w, const uint8_t* msgs, const uint32_t* msg_off, const uint32_t* item_msg,
+                       hipStream_t st) {
+  if ((w.msg_bytes && hipMemcpyAsync(w.msgs, msgs, w.msg_bytes, hipMemcpyHostToDevice, st) != hipSuccess) ||
+      hipMemcpyAsync(w.msg_off, msg_off, 4ull * (w.n_msgs + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(w.item_msg, item_msg, 4ull * w.n, hipMemcpyHostToDevice, st) != hipSuccess)
+    return TBG_E_DEVICE;
+  return TBG_OK;
+}
+
+// H(m) of the call's messages into w.h_aff / w.h_status.
+void hash_call_msgs(const SignWork& w, hipStream_t st) {
+  DevBatch B{};
+  memset(&B, 0, sizeof(B));
+  B.n_msgs = (uint32_t)w.n_msgs;
+  B.msgs = w.msgs;
+  B.msg_off = w.msg_off;
+  B.h_aff = w.h_aff;
+  B.h_status = w.h_status;
+  B.h_jac = w.h_jac;
+  launch_hash_msgs(B, st);
+}
+
+}  // namespace
+
 extern "C" {
 
 int tbg_sk_to_pk(tbg_ctx* c, const uint8_t* sk32, uint32_t n, uint8_t* pk48) {
@@ -1392,73 +1464,46 @@ int tbg_sk_to_pk(tbg_ctx* c, const uint8_t* sk32, uint32_t n, uint8_t* pk48) {
   if (n == 0) return TBG_OK;
   std::lock_guard<std::mutex> lk(c->mu);
   HIP_TRY(hipSetDevice(c->device));
-  uint8_t *d_sk = nullptr, *d_pk = nullptr;
-  if (hipMalloc(&d_sk, 32ull * n) != hipSuccess) return TBG_E_OOM;
-  if (hipMalloc(&d_pk, 48ull * n) != hipSuccess) { hipFree(d_sk); return TBG_E_OOM; }
-  int rc = TBG_OK;
-  if (hipMemcpyAsync(d_sk, sk32, 32ull * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = TBG_E_DEVICE;
+  SkToPkWork w;
+  w.n = n;
+  CallScope cs(c->stream);
+  int rc = cs.open(w);
+  if (rc != TBG_OK) return rc;
+  hipStream_t st = c->stream;
+  if (hipMemcpyAsync(w.sk, sk32, 32ull * n, hipMemcpyHostToDevice, st) != hipSuccess) rc = TBG_E_DEVICE;
   if (rc == TBG_OK) {
-    launch_sk_to_pk(d_sk, n, d_pk, c->stream);
+    launch_sk_to_pk(w.sk, n, w.pk, st);
     if (hipGetLastError() != hipSuccess) rc = TBG_E_DEVICE;
   }
-  if (rc == TBG_OK && hipMemcpyAsync(pk48, d_pk, 48ull * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = TBG_E_DEVICE;
-  if (hipStreamSynchronize(c->stream) != hipSuccess) rc = TBG_E_DEVICE;
-  hipFree(d_sk);
-  hipFree(d_pk);
-  return rc;
+  if (rc == TBG_OK && hipMemcpyAsync(pk48, w.pk, 48ull * n, hipMemcpyDeviceToHost, st) != hipSuccess) rc = TBG_E_DEVICE;
+  return cs.drain(rc);
 }
 
 int tbg_sign(tbg_ctx* c, const uint8_t* sk32, uint32_t n, const uint8_t* msgs, const uint32_t* msg_off, uint32_t n_msgs,
              const uint32_t* item_msg, uint8_t* sig96) {
-  if (!c || (n && (!sk32 || !sig96 || !item_msg)) || n_msgs == 0 || !msg_off) return TBG_E_INVALID_ARG;
-  if (msg_off[0] != 0) return TBG_E_INVALID_ARG;
-  for (uint32_t m = 0; m < n_msgs; ++m)
-    if (msg_off[m + 1] < msg_off[m]) return TBG_E_INVALID_ARG;
+  if (!c || (n && (!sk32 || !sig96 || !item_msg)) || n_msgs == 0 || !offsets_ok(msg_off, n_msgs)) return TBG_E_INVALID_ARG;
   for (uint32_t i = 0; i < n; ++i)
     if (item_msg[i] >= n_msgs) return TBG_E_INVALID_ARG;
   if (n == 0) return TBG_OK;
   std::lock_guard<std::mutex> lk(c->mu);
   HIP_TRY(hipSetDevice(c->device));
-  size_t mb = msg_off[n_msgs];
-  size_t need = align_up(32ull * n, 16) + align_up(mb + 1, 16) + align_up(4ull * (n_msgs + 1), 16) + align_up(4ull * n, 16) +
-                align_up(sizeof(G2A) * (size_t)n_msgs, 16) + align_up(4ull * n_msgs, 16) + align_up(96ull * n, 16) +
-                align_up(3 * sizeof(G2J) * (size_t)n_msgs, 16);
-  uint8_t* base = nullptr;
-  if (hipMalloc(&base, need) != hipSuccess) return TBG_E_OOM;
-  Arena a;
-  auto sec = [&](size_t bytes) { return base + a.take(bytes); };
-  uint8_t* d_sk = sec(32ull * n);
-  uint8_t* d_msgs = sec(mb + 1);
-  uint32_t* d_off = (uint32_t*)sec(4ull * (n_msgs + 1));
-  uint32_t* d_im = (uint32_t*)sec(4ull * n);
-  G2A* d_h = (G2A*)sec(sizeof(G2A) * (size_t)n_msgs);
-  int32_t* d_hs = (int32_t*)sec(4ull * n_msgs);
-  uint8_t* d_sig = sec(96ull * n);
-  G2J* d_hj = (G2J*)sec(3 * sizeof(G2J) * (size_t)n_msgs);
-  int rc = TBG_OK;
+  SignWork w;
+  w.n = n;
+  w.n_msgs = n_msgs;
+  w.msg_bytes = msg_off[n_msgs];
+  CallScope cs(c->stream);
+  int rc = cs.open(w);
+  if (rc != TBG_OK) return rc;
   hipStream_t st = c->stream;
-  if (hipMemcpyAsync(d_sk, sk32, 32ull * n, hipMemcpyHostToDevice, st) != hipSuccess ||
-      (mb && hipMemcpyAsync(d_msgs, msgs, mb, hipMemcpyHostToDevice, st) != hipSuccess) ||
-      hipMemcpyAsync(d_off, msg_off, 4ull * (n_msgs + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(d_im, item_msg, 4ull * n, hipMemcpyHostToDevice, st) != hipSuccess)
-    rc = TBG_E_DEVICE;
+  if (hipMemcpyAsync(w.sk, sk32, 32ull * n, hipMemcpyHostToDevice, st) != hipSuccess) rc = TBG_E_DEVICE;
+  if (rc == TBG_OK) rc = upload_sign_inputs(w, msgs, msg_off, item_msg, st);
   if (rc == TBG_OK) {
-    DevBatch B{};
-    memset(&B, 0, sizeof(B));
-    B.n_msgs = n_msgs;
-    B.msgs = d_msgs;
-    B.msg_off = d_off;
-    B.h_aff = d_h;
-    B.h_status = d_hs;
-    B.h_jac = d_hj;
-    launch_hash_msgs(B, st);
-    launch_sign(d_sk, d_im, n, d_h, d_hs, d_sig, st);
+    hash_call_msgs(w, st);
+    launch_sign(w.sk, w.item_msg, n, w.h_aff, w.h_status, w.sig, st);
     if (hipGetLastError() != hipSuccess) rc = TBG_E_DEVICE;
   }
-  if (rc == TBG_OK && hipMemcpyAsync(sig96, d_sig, 96ull * n, hipMemcpyDeviceToHost, st) != hipSuccess) rc = TBG_E_DEVICE;
-  if (hipStreamSynchronize(st) != hipSuccess) rc = TBG_E_DEVICE;
-  hipFree(base);
-  return rc;
+  if (rc == TBG_OK && hipMemcpyAsync(sig96, w.sig, 96ull * n, hipMemcpyDeviceToHost, st) != hipSuccess) rc = TBG_E_DEVICE;
+  return cs.drain(rc);
 }
 
 }  // extern "C"
@@ -1489,18 +1534,17 @@ void keyed_wipe(void* p, size_t n) {
   for (size_t i = 0; i < n; ++i) v[i] = 0;
 }
 
-// Everything of one hardened call that held key bytes: the device copy of the
-// keys (inside the call's workspace) and the pinned staging they were
-// uploaded from.  Whatever way the call ends, the device bytes are zeroed ON
-// THE STREAM (behind the kernels that read them), the stream is drained, the
-// staging is zeroed, and only then is either released.
-struct KeyedScope {
-  hipStream_t st = nullptr;
-  uint8_t* d_base = nullptr;  // the workspace (hipMalloc)
-  uint8_t* d_sk = nullptr;    // [sk_bytes] inside it
-  uint8_t* h_sk = nullptr;    // [sk_bytes] pinned (hipHostMalloc)
+// The scope of a hardened call: CallScope and everything that held key bytes
+// -- the device copy of the keys (the workspace's `sk` section) and the pinned
+// staging they were uploaded from.  Whatever way the call ends, the device
+// bytes are zeroed ON THE STREAM (behind the kernels that read them), the
+// stream is drained, the staging is zeroed, and only then is either released
+// (the workspace by ~CallScope, which runs after this destructor).
+struct KeyedScope : CallScope {
+  uint8_t* d_sk = nullptr;  // [sk_bytes] inside the workspace
+  uint8_t* h_sk = nullptr;  // [sk_bytes] pinned (hipHostMalloc)
   size_t sk_bytes = 0;
-  Arena arena;
+  using CallScope::CallScope;
   ~KeyedScope() {
     if (d_sk) (void)hipMemsetAsync(d_sk, 0, sk_bytes, st);
     (void)hipStreamSynchronize(st);
@@ -1508,15 +1552,14 @@ struct KeyedScope {
       keyed_wipe(h_sk, sk_bytes);
       (void)hipHostFree(h_sk);
     }
-    if (d_base) (void)hipFree(d_base);
   }
-  uint8_t* sec(size_t bytes) { return d_base + arena.take(bytes); }
-  // The workspace and the staging; the keys go into the staging with every
+  // w's workspace and the staging; the keys go into the staging with every
   // rejected one replaced by 1 (masks, no branch on a key byte), their codes into kst.
-  int open(hipStream_t stream, size_t work_bytes, const uint8_t* sk32, uint32_t n, std::vector<int32_t>& kst) {
-    st = stream;
+  template <class W>
+  int open(W& w, const uint8_t* sk32, uint32_t n, std::vector<int32_t>& kst) {
     sk_bytes = 32ull * n;
-    if (hipMalloc(&d_base, work_bytes) != hipSuccess) { d_base = nullptr; return TBG_E_OOM; }
+    const int rc = CallScope::open(w);
+    if (rc != TBG_OK) return rc;
     if (hipHostMalloc((void**)&h_sk, sk_bytes, hipHostMallocDefault) != hipSuccess) { h_sk = nullptr; return TBG_E_OOM; }
     kst.resize(n);
     for (uint32_t i = 0; i < n; ++i) {
@@ -1525,7 +1568,7 @@ struct KeyedScope {
       const uint8_t keep = (uint8_t)(((uint32_t)kst[i] | (0u - (uint32_t)kst[i])) >> 31) - 1;  // 0xff: accepted
       for (int j = 0; j < 32; ++j) h_sk[32ull * i + j] = (uint8_t)((k[j] & keep) | ((j == 31 ? 1 : 0) & ~keep));
     }
-    d_sk = sec(sk_bytes);
+    d_sk = w.sk;
     return hipMemcpyAsync(d_sk, h_sk, sk_bytes, hipMemcpyHostToDevice, st) == hipSuccess ? TBG_OK : TBG_E_DEVICE;
   }
 };
@@ -1548,80 +1591,55 @@ int tbg_sk_to_pk_ct(tbg_ctx* c, const uint8_t* sk32, uint32_t n, uint8_t* pk48, 
   if (n == 0) return TBG_OK;
   std::lock_guard<std::mutex> lk(c->mu);
   HIP_TRY(hipSetDevice(c->device));
-  const size_t tab_bytes = 4 * ct_tab_words_g1();
+  SkToPkCtWork w;
+  w.n = n;
+  w.tab_words = ct_tab_words_g1();
   std::vector<int32_t> kst;
-  KeyedScope ks;
-  int rc = ks.open(c->stream, align_up(32ull * n, 16) + align_up(tab_bytes, 16) + align_up(48ull * n, 16) +
-                                  align_up(4ull * n, 16), sk32, n, kst);
+  KeyedScope ks(c->stream);
+  int rc = ks.open(w, sk32, n, kst);
   if (rc != TBG_OK) return rc;
   hipStream_t st = c->stream;
-  uint32_t* d_tab = (uint32_t*)ks.sec(tab_bytes);
-  uint8_t* d_pk = ks.sec(48ull * n);
-  int32_t* d_st = (int32_t*)ks.sec(4ull * n);
-  launch_ct_table_g1(d_tab, st);
-  launch_sk_to_pk_ct(ks.d_sk, n, d_tab, d_pk, d_st, st);
+  launch_ct_table_g1(w.tab, st);
+  launch_sk_to_pk_ct(w.sk, n, w.tab, w.pk, w.status, st);
   if (hipGetLastError() != hipSuccess) rc = TBG_E_DEVICE;
-  if (rc == TBG_OK && (hipMemcpyAsync(pk48, d_pk, 48ull * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                       hipMemcpyAsync(status, d_st, 4ull * n, hipMemcpyDeviceToHost, st) != hipSuccess))
+  if (rc == TBG_OK && (hipMemcpyAsync(pk48, w.pk, 48ull * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                       hipMemcpyAsync(status, w.status, 4ull * n, hipMemcpyDeviceToHost, st) != hipSuccess))
     rc = TBG_E_DEVICE;
-  if (hipStreamSynchronize(st) != hipSuccess) rc = TBG_E_DEVICE;
+  rc = ks.drain(rc);
   if (rc == TBG_OK) keyed_mask(kst, pk48, 48, status);
   return rc;
 }
 
 int tbg_sign_ct(tbg_ctx* c, const uint8_t* sk32, uint32_t n, const uint8_t* msgs, const uint32_t* msg_off, uint32_t n_msgs,
                 const uint32_t* item_msg, uint8_t* sig96, int32_t* status) {
-  if (!c || (n && (!sk32 || !sig96 || !item_msg || !status)) || n_msgs == 0 || !msg_off) return TBG_E_INVALID_ARG;
-  if (msg_off[0] != 0) return TBG_E_INVALID_ARG;
-  for (uint32_t m = 0; m < n_msgs; ++m)
-    if (msg_off[m + 1] < msg_off[m]) return TBG_E_INVALID_ARG;
+  if (!c || (n && (!sk32 || !sig96 || !item_msg || !status)) || n_msgs == 0 || !offsets_ok(msg_off, n_msgs))
+    return TBG_E_INVALID_ARG;
   for (uint32_t i = 0; i < n; ++i)
     if (item_msg[i] >= n_msgs) return TBG_E_INVALID_ARG;
   if (n == 0) return TBG_OK;
   std::lock_guard<std::mutex> lk(c->mu);
   HIP_TRY(hipSetDevice(c->device));
-  const size_t mb = msg_off[n_msgs];
-  const size_t tab_bytes = 4 * ct_tab_words_g2(n_msgs);
-  const size_t need = align_up(32ull * n, 16) + align_up(mb + 1, 16) + align_up(4ull * (n_msgs + 1), 16) +
-                      align_up(4ull * n, 16) + align_up(sizeof(G2A) * (size_t)n_msgs, 16) + align_up(4ull * n_msgs, 16) +
-                      align_up(96ull * n, 16) + align_up(3 * sizeof(G2J) * (size_t)n_msgs, 16) + align_up(tab_bytes, 16) +
-                      align_up(4ull * n, 16);
+  SignCtWork w;
+  w.n = n;
+  w.n_msgs = n_msgs;
+  w.msg_bytes = msg_off[n_msgs];
+  w.tab_words = ct_tab_words_g2(n_msgs);
   std::vector<int32_t> kst;
-  KeyedScope ks;
-  int rc = ks.open(c->stream, need, sk32, n, kst);
+  KeyedScope ks(c->stream);
+  int rc = ks.open(w, sk32, n, kst);
   if (rc != TBG_OK) return rc;
   hipStream_t st = c->stream;
-  uint8_t* d_msgs = ks.sec(mb + 1);
-  uint32_t* d_off = (uint32_t*)ks.sec(4ull * (n_msgs + 1));
-  uint32_t* d_im = (uint32_t*)ks.sec(4ull * n);
-  G2A* d_h = (G2A*)ks.sec(sizeof(G2A) * (size_t)n_msgs);
-  int32_t* d_hs = (int32_t*)ks.sec(4ull * n_msgs);
-  uint8_t* d_sig = ks.sec(96ull * n);
-  G2J* d_hj = (G2J*)ks.sec(3 * sizeof(G2J) * (size_t)n_msgs);
-  uint32_t* d_tab = (uint32_t*)ks.sec(tab_bytes);
-  int32_t* d_st = (int32_t*)ks.sec(4ull * n);
-  if ((mb && hipMemcpyAsync(d_msgs, msgs, mb, hipMemcpyHostToDevice, st) != hipSuccess) ||
-      hipMemcpyAsync(d_off, msg_off, 4ull * (n_msgs + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(d_im, item_msg, 4ull * n, hipMemcpyHostToDevice, st) != hipSuccess)
-    rc = TBG_E_DEVICE;
+  rc = upload_sign_inputs(w, msgs, msg_off, item_msg, st);
   if (rc == TBG_OK) {
-    DevBatch B{};
-    memset(&B, 0, sizeof(B));
-    B.n_msgs = n_msgs;
-    B.msgs = d_msgs;
-    B.msg_off = d_off;
-    B.h_aff = d_h;
-    B.h_status = d_hs;
-    B.h_jac = d_hj;
-    launch_hash_msgs(B, st);
-    launch_ct_table_g2(d_h, d_hs, n_msgs, d_tab, st);
-    launch_sign_ct(ks.d_sk, d_im, n, n_msgs, d_tab, d_hs, d_sig, d_st, st);
+    hash_call_msgs(w, st);
+    launch_ct_table_g2(w.h_aff, w.h_status, n_msgs, w.tab, st);
+    launch_sign_ct(w.sk, w.item_msg, n, n_msgs, w.tab, w.h_status, w.sig, w.status, st);
     if (hipGetLastError() != hipSuccess) rc = TBG_E_DEVICE;
   }
-  if (rc == TBG_OK && (hipMemcpyAsync(sig96, d_sig, 96ull * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                       hipMemcpyAsync(status, d_st, 4ull * n, hipMemcpyDeviceToHost, st) != hipSuccess))
+  if (rc == TBG_OK && (hipMemcpyAsync(sig96, w.sig, 96ull * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                       hipMemcpyAsync(status, w.status, 4ull * n, hipMemcpyDeviceToHost, st) != hipSuccess))
     rc = TBG_E_DEVICE;
-  if (hipStreamSynchronize(st) != hipSuccess) rc = TBG_E_DEVICE;
+  rc = ks.drain(rc);
   if (rc == TBG_OK) keyed_mask(kst, sig96, 96, status);
   return rc;
 }
@@ -1634,31 +1652,9 @@ int tbg_sign_ct(tbg_ctx* c, const uint8_t* sk32, uint32_t n, const uint8_t* msgs
 
 namespace {
 
-// One device allocation for a utility call, freed on scope exit.
-struct DevArena {
-  uint8_t* base = nullptr;
-  Arena arena;
-  ~DevArena() {
-    if (base) hipFree(base);
-  }
-  int alloc(size_t bytes) { return hipMalloc(&base, bytes ? bytes : 16) == hipSuccess ? TBG_OK : TBG_E_OOM; }
-  uint8_t* sec(size_t bytes) { return base + arena.take(bytes); }
-};
-
-bool offsets_ok(const uint32_t* off, uint32_t n_sets) {
-  if (!off || off[0] != 0) return false;
-  for (uint32_t s = 0; s < n_sets; ++s)
-    if (off[s + 1] < off[s]) return false;
-  return true;
-}
-
-// Host half of a sum plan and its device copy inside `a`.
+// Host half of a sum plan; its device half is the head of the call's workspace (SumWork).
 struct SumHost {
   std::vector<uint32_t> chunk_first, chunk_set;
-  static size_t bytes(uint32_t n_sets, uint32_t n_chunks, size_t part_elem) {
-    return align_up(4ull * (n_sets + 1), 16) * 2 + align_up(4ull * n_chunks + 4, 16) +
-           align_up(part_elem * n_chunks + 16, 16) + align_up(4ull * n_sets + 4, 16);
-  }
   SumHost(const uint32_t* off, uint32_t n_sets) {
     const uint32_t ch = tbg::sum_chunk_size();
     chunk_first.resize(n_sets + 1);
@@ -1670,21 +1666,26 @@ struct SumHost {
     }
   }
   uint32_t n_chunks() const { return chunk_first.back(); }
-  int upload(DevArena& a, const uint32_t* off, uint32_t n_sets, size_t part_elem, hipStream_t st, tbg::SumPlan& p) {
-    uint32_t* d_off = (uint32_t*)a.sec(4ull * (n_sets + 1));
-    uint32_t* d_cf = (uint32_t*)a.sec(4ull * (n_sets + 1));
-    uint32_t* d_cs = (uint32_t*)a.sec(4ull * n_chunks() + 4);
-    p.part = a.sec(part_elem * n_chunks() + 16);
-    p.set_bad = (int32_t*)a.sec(4ull * n_sets + 4);
+  // the counts of the plan's device half, part_elem bytes per chunk sum (before the workspace is opened)
+  void describe(SumWork& w, uint32_t n_sets, size_t part_elem) const {
+    w.n_sets = n_sets;
+    w.n_chunks = n_chunks();
+    w.part_elem = part_elem;
+  }
+  int upload(const SumWork& w, const uint32_t* off, hipStream_t st, tbg::SumPlan& p) const {
+    const uint32_t n_sets = (uint32_t)w.n_sets;
     p.n_sets = n_sets;
     p.n_chunks = n_chunks();
-    p.off = d_off;
-    p.chunk_first = d_cf;
-    p.chunk_set = d_cs;
-    if (hipMemcpyAsync(d_off, off, 4ull * (n_sets + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(d_cf, chunk_first.data(), 4ull * (n_sets + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
-        (n_chunks() && hipMemcpyAsync(d_cs, chunk_set.data(), 4ull * n_chunks(), hipMemcpyHostToDevice, st) != hipSuccess) ||
-        hipMemsetAsync(p.set_bad, 0, 4ull * n_sets, st) != hipSuccess)
+    p.off = w.off;
+    p.chunk_first = w.chunk_first;
+    p.chunk_set = w.chunk_set;
+    p.part = w.part;
+    p.set_bad = w.set_bad;
+    if (hipMemcpyAsync(w.off, off, 4ull * (n_sets + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(w.chunk_first, chunk_first.data(), 4ull * (n_sets + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
+        (n_chunks() &&
+         hipMemcpyAsync(w.chunk_set, chunk_set.data(), 4ull * n_chunks(), hipMemcpyHostToDevice, st) != hipSuccess) ||
+        hipMemsetAsync(w.set_bad, 0, 4ull * n_sets, st) != hipSuccess)
       return TBG_E_DEVICE;
     return TBG_OK;
   }
@@ -1701,24 +1702,26 @@ int tbg_sum_pubkeys(tbg_ctx* c, const uint32_t* pubkey_ids, const uint32_t* off,
   if (ni && !pubkey_ids) return TBG_E_INVALID_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   HIP_TRY(hipSetDevice(c->device));
-  SumHost h(off, n_sets);
-  DevArena a;
-  int rc = a.alloc(SumHost::bytes(n_sets, h.n_chunks(), sizeof(G1J)) + align_up(4ull * ni + 4, 16) +
-                   align_up(48ull * n_sets, 16) + align_up(4ull * n_sets, 16));
+  const SumHost h(off, n_sets);  // (outlives the scope: its vectors are copied from on the stream)
+  SumPubkeysWork w;
+  h.describe(w, n_sets, sizeof(G1J));
+  w.n_items = ni;
+  CallScope cs(c->stream);
+  int rc = cs.open(w);
   if (rc != TBG_OK) return rc;
   hipStream_t st = c->stream;
   tbg::SumPlan p;
-  if ((rc = h.upload(a, off, n_sets, sizeof(G1J), st, p)) != TBG_OK) return rc;
-  uint32_t* d_ids = (uint32_t*)a.sec(4ull * ni + 4);
-  uint8_t* d_out = a.sec(48ull * n_sets);
-  int32_t* d_st = (int32_t*)a.sec(4ull * n_sets);
-  if (ni) HIP_TRY(hipMemcpyAsync(d_ids, pubkey_ids, 4ull * ni, hipMemcpyHostToDevice, st));
-  tbg::launch_sum_g1(c->d_pk, c->d_pk_status, c->n_pk, d_ids, p, d_out, d_st, st);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out48, d_out, 48ull * n_sets, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(status, d_st, 4ull * n_sets, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return TBG_OK;
+  rc = h.upload(w, off, st, p);
+  if (rc == TBG_OK && ni && hipMemcpyAsync(w.ids, pubkey_ids, 4ull * ni, hipMemcpyHostToDevice, st) != hipSuccess)
+    rc = TBG_E_DEVICE;
+  if (rc == TBG_OK) {
+    tbg::launch_sum_g1(c->d_pk, c->d_pk_status, c->n_pk, w.ids, p, w.out, w.status, st);
+    if (hipGetLastError() != hipSuccess) rc = TBG_E_DEVICE;
+  }
+  if (rc == TBG_OK && (hipMemcpyAsync(out48, w.out, 48ull * n_sets, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                       hipMemcpyAsync(status, w.status, 4ull * n_sets, hipMemcpyDeviceToHost, st) != hipSuccess))
+    rc = TBG_E_DEVICE;
+  return cs.drain(rc);
 }
 
 int tbg_sum_sigs(tbg_ctx* c, const uint8_t* sigs96, const uint32_t* off, uint32_t n_sets, uint8_t* out96,
@@ -1728,26 +1731,28 @@ int tbg_sum_sigs(tbg_ctx* c, const uint8_t* sigs96, const uint32_t* off, uint32_
   if (ni && !sigs96) return TBG_E_INVALID_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   HIP_TRY(hipSetDevice(c->device));
-  SumHost h(off, n_sets);
-  DevArena a;
-  int rc = a.alloc(SumHost::bytes(n_sets, h.n_chunks(), sizeof(G2J)) + align_up(96ull * ni + 4, 16) +
-                   align_up(4ull * ni + 4, 16) + align_up(96ull * n_sets, 16) + align_up(4ull * n_sets, 16));
+  const SumHost h(off, n_sets);  // (outlives the scope: its vectors are copied from on the stream)
+  SumSigsWork w;
+  h.describe(w, n_sets, sizeof(G2J));
+  w.n_items = ni;
+  CallScope cs(c->stream);
+  int rc = cs.open(w);
   if (rc != TBG_OK) return rc;
   hipStream_t st = c->stream;
   tbg::SumPlan p;
-  if ((rc = h.upload(a, off, n_sets, sizeof(G2J), st, p)) != TBG_OK) return rc;
-  uint8_t* d_sigs = a.sec(96ull * ni + 4);
-  int32_t* d_sst = (int32_t*)a.sec(4ull * ni + 4);
-  uint8_t* d_out = a.sec(96ull * n_sets);
-  int32_t* d_st = (int32_t*)a.sec(4ull * n_sets);
-  if (ni) HIP_TRY(hipMemcpyAsync(d_sigs, sigs96, 96ull * ni, hipMemcpyHostToDevice, st));
-  tbg::launch_sum_g2(d_sigs, p, d_out, d_st, d_sst, st);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out96, d_out, 96ull * n_sets, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(status, d_st, 4ull * n_sets, hipMemcpyDeviceToHost, st));
-  if (sig_status && ni) HIP_TRY(hipMemcpyAsync(sig_status, d_sst, 4ull * ni, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return TBG_OK;
+  rc = h.upload(w, off, st, p);
+  if (rc == TBG_OK && ni && hipMemcpyAsync(w.sigs, sigs96, 96ull * ni, hipMemcpyHostToDevice, st) != hipSuccess)
+    rc = TBG_E_DEVICE;
+  if (rc == TBG_OK) {
+    tbg::launch_sum_g2(w.sigs, p, w.out, w.status, w.sig_status, st);
+    if (hipGetLastError() != hipSuccess) rc = TBG_E_DEVICE;
+  }
+  if (rc == TBG_OK &&
+      (hipMemcpyAsync(out96, w.out, 96ull * n_sets, hipMemcpyDeviceToHost, st) != hipSuccess ||
+       hipMemcpyAsync(status, w.status, 4ull * n_sets, hipMemcpyDeviceToHost, st) != hipSuccess ||
+       (sig_status && ni && hipMemcpyAsync(sig_status, w.sig_status, 4ull * ni, hipMemcpyDeviceToHost, st) != hipSuccess)))
+    rc = TBG_E_DEVICE;
+  return cs.drain(rc);
 }
 
 int tbg_fast_aggregate_verify(tbg_ctx* c, const uint32_t* pubkey_ids, const uint32_t* key_off, uint32_t n_sets,
@@ -1760,73 +1765,68 @@ int tbg_fast_aggregate_verify(tbg_ctx* c, const uint32_t* pubkey_ids, const uint
   std::lock_guard<std::mutex> lk(c->mu);
   HIP_TRY(hipSetDevice(c->device));
   const uint32_t n = n_sets;
-  SumHost h(key_off, n);
+  // (both outlive the scope: they are copied from on the stream)
+  const SumHost h(key_off, n);
   std::vector<uint32_t> iota(n + 1);
   for (uint32_t i = 0; i <= n; ++i) iota[i] = i;
-  const size_t lines = 4ull * LINES_WORDS * n;
-  DevArena a;
-  int rc = a.alloc(SumHost::bytes(n, h.n_chunks(), sizeof(G1J)) + align_up(4ull * nk + 4, 16) +
-                   align_up(48ull * n, 16) * 2 + align_up(sizeof(G1A) * n, 16) * 2 + align_up(4ull * n, 16) * 6 +
-                   align_up(mb + 1, 16) + align_up(4ull * (n + 1), 16) * 2 + align_up(96ull * n, 16) + align_up(n, 16) +
-                   align_up(sizeof(G2A) * n, 16) * 2 + align_up(3 * sizeof(G2J) * n, 16) + 2 * align_up(lines, 16) +
-                   align_up(4ull * tbg::CNT_WORDS, 16));
+  FastAggVerifyWork w;
+  h.describe(w, n, sizeof(G1J));
+  w.n_keys = nk;
+  w.msg_bytes = mb;
+  CallScope cs(c->stream);
+  int rc = cs.open(w);
   if (rc != TBG_OK) return rc;
   hipStream_t st = c->stream;
   // 1. the key sums, compressed, then decoded into a table of their own
   tbg::SumPlan p;
-  if ((rc = h.upload(a, key_off, n, sizeof(G1J), st, p)) != TBG_OK) return rc;
-  uint32_t* d_ids = (uint32_t*)a.sec(4ull * nk + 4);
-  uint8_t* d_pk48 = a.sec(48ull * n);
-  int32_t* d_kst = (int32_t*)a.sec(4ull * n);
-  G1A* t_pk = (G1A*)a.sec(sizeof(G1A) * n);
-  G1A* t_xpk = (G1A*)a.sec(sizeof(G1A) * n);
-  int32_t* t_pkst = (int32_t*)a.sec(4ull * n);
-  if (nk) HIP_TRY(hipMemcpyAsync(d_ids, pubkey_ids, 4ull * nk, hipMemcpyHostToDevice, st));
-  tbg::launch_sum_g1(c->d_pk, c->d_pk_status, c->n_pk, d_ids, p, d_pk48, d_kst, st);
-  tbg::launch_decode_pubkeys(d_pk48, n, t_pk, t_xpk, t_pkst, st);  // a failed / identity sum: not DEC_OK
+  rc = h.upload(w, key_off, st, p);
+  if (rc == TBG_OK && nk && hipMemcpyAsync(w.ids, pubkey_ids, 4ull * nk, hipMemcpyHostToDevice, st) != hipSuccess)
+    rc = TBG_E_DEVICE;
+  if (rc == TBG_OK) {
+    tbg::launch_sum_g1(c->d_pk, c->d_pk_status, c->n_pk, w.ids, p, w.pk48, w.key_status, st);
+    tbg::launch_decode_pubkeys(w.pk48, n, w.t_pk, w.t_xpk, w.t_pk_status, st);  // a failed / identity sum: not DEC_OK
+  }
   // 2. one CoreVerify per set against that table (the per-item schedule)
   DevBatch B{};
   memset(&B, 0, sizeof(B));
   B.op = TBG_OP_VERIFY;
   B.n_duties = B.n_partials = B.n_msgs = n;
-  uint8_t* d_msgs = a.sec(mb + 1);
-  uint32_t* d_moff = (uint32_t*)a.sec(4ull * (n + 1));
-  uint32_t* d_iota = (uint32_t*)a.sec(4ull * (n + 1));
-  uint8_t* d_sigs = a.sec(96ull * n);
-  uint8_t* d_idf = a.sec(n);
-  B.msgs = d_msgs;
-  B.msg_off = d_moff;
-  B.duty_msg = B.duty_first = B.partial_duty = B.pubkey_ids = d_iota;
-  B.duty_threshold = d_iota;  // unused by TBG_OP_VERIFY
-  B.sigs = d_sigs;
-  B.identifiers = d_idf;
-  B.sig_aff = (G2A*)a.sec(sizeof(G2A) * n);
-  B.h_aff = (G2A*)a.sec(sizeof(G2A) * n);
-  B.h_status = (int32_t*)a.sec(4ull * n);
-  B.h_jac = (G2J*)a.sec(3 * sizeof(G2J) * n);
-  B.sig_lines = (uint32_t*)a.sec(lines);
-  B.h_lines = (uint32_t*)a.sec(lines);
-  B.counters = (uint32_t*)a.sec(4ull * tbg::CNT_WORDS);
-  B.part_list = (uint32_t*)a.sec(4ull * n);
-  B.partial_status = (int32_t*)a.sec(4ull * n);
-  B.duty_status = (int32_t*)a.sec(4ull * n);
+  B.msgs = w.msgs;
+  B.msg_off = w.msg_off;
+  B.duty_msg = B.duty_first = B.partial_duty = B.pubkey_ids = w.iota;
+  B.duty_threshold = w.iota;  // unused by TBG_OP_VERIFY
+  B.sigs = w.sigs;
+  B.identifiers = w.identifiers;
+  B.sig_aff = w.sig_aff;
+  B.h_aff = w.h_aff;
+  B.h_status = w.h_status;
+  B.h_jac = w.h_jac;
+  B.sig_lines = w.sig_lines;
+  B.h_lines = w.h_lines;
+  B.counters = w.counters;
+  B.part_list = w.part_list;
+  B.partial_status = w.partial_status;
+  B.duty_status = w.duty_status;
   B.rlc_group = 0;
   B.fb_full = 0xFFFFFFFFu;
-  if (mb) HIP_TRY(hipMemcpyAsync(d_msgs, msgs, mb, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_moff, msg_off, 4ull * (n + 1), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_iota, iota.data(), 4ull * (n + 1), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_sigs, sigs96, 96ull * n, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(d_idf, 0, n, st));
-  HIP_TRY(hipMemsetAsync(B.counters, 0, 4 * tbg::CNT_WORDS, st));
-  tbg::launch_decode_sigs(B, st);
-  tbg::launch_hash_msgs(B, st);
-  tbg::launch_h_lines(B, st);
-  tbg::launch_rlc_prepare(B, t_pk, nullptr, t_pkst, n, st);
-  tbg::launch_rlc_check(B, t_pk, nullptr, t_pkst, n, st);  // (per-item schedule: no key table)
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(status, B.partial_status, 4ull * n, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return TBG_OK;
+  if (rc == TBG_OK && ((mb && hipMemcpyAsync(w.msgs, msgs, mb, hipMemcpyHostToDevice, st) != hipSuccess) ||
+                       hipMemcpyAsync(w.msg_off, msg_off, 4ull * (n + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
+                       hipMemcpyAsync(w.iota, iota.data(), 4ull * (n + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
+                       hipMemcpyAsync(w.sigs, sigs96, 96ull * n, hipMemcpyHostToDevice, st) != hipSuccess ||
+                       hipMemsetAsync(w.identifiers, 0, n, st) != hipSuccess ||
+                       hipMemsetAsync(w.counters, 0, 4 * tbg::CNT_WORDS, st) != hipSuccess))
+    rc = TBG_E_DEVICE;
+  if (rc == TBG_OK) {
+    tbg::launch_decode_sigs(B, st);
+    tbg::launch_hash_msgs(B, st);
+    tbg::launch_h_lines(B, st);
+    tbg::launch_rlc_prepare(B, w.t_pk, nullptr, w.t_pk_status, n, st);
+    tbg::launch_rlc_check(B, w.t_pk, nullptr, w.t_pk_status, n, st);  // (per-item schedule: no key table)
+    if (hipGetLastError() != hipSuccess) rc = TBG_E_DEVICE;
+  }
+  if (rc == TBG_OK && hipMemcpyAsync(status, w.partial_status, 4ull * n, hipMemcpyDeviceToHost, st) != hipSuccess)
+    rc = TBG_E_DEVICE;
+  return cs.drain(rc);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 """Host (CPU) build of the launch plan and the arena section table
-(charon_amd/csrc/tbls_plan.h), for tests/test_plan_host.py.
+(charon_amd/csrc/tbls_plan.h) and of the one-shot calls' workspaces
+(tbls_work.h), for tests/test_plan_host.py.
 
 TEST TOOLING ONLY -- see plan_host.cpp.  Built on demand with the ROCm clang
 (host target); the header makes no HIP runtime call, it only reads the HIP
@@ -56,5 +57,9 @@ def lib():
         h.pl_l0_shape.argtypes = [q, u, i, u, u, u, u, p, u, p]
         h.pl_sgb_plan.restype = i
         h.pl_sgb_plan.argtypes = [d, p]
+        h.pl_max_work_sections.restype = u
+        h.pl_max_work_sections.argtypes = []
+        h.pl_work.restype = i
+        h.pl_work.argtypes = [u, p, q, p, p, p, p]
         _lib = h
     return _lib

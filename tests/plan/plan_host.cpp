@@ -1,11 +1,13 @@
 // TEST TOOLING ONLY: C entry points over charon_amd/csrc/tbls_plan.h -- the
 // launch plan, the section layout, bind over fake base addresses and the
-// replay fit rule -- for tests/test_plan_host.py.  Plain host C++: the header
-// makes no HIP runtime call.
+// replay fit rule -- and over tbls_work.h, the workspaces of the one-shot
+// calls, for tests/test_plan_host.py.  Plain host C++: the headers make no
+// HIP runtime call.
 #include <cstdint>
 #include <cstring>
 #include <vector>
 #include "../../charon_amd/csrc/tbls_plan.h"
+#include "../../charon_amd/csrc/tbls_work.h"
 
 using namespace tbg;
 
@@ -147,5 +149,84 @@ void pl_l0_shape(uint64_t nd, uint32_t n_simd, int g_free, uint32_t G, uint32_t 
 }
 
 int pl_sgb_plan(double rho, uint32_t* m) { return sgb_plan(rho, *m) ? 1 : 0; }
+
+uint32_t pl_max_work_sections() { return kMaxWorkSections; }
+
+// The workspace of one-shot call `call` (0 tbg_sk_to_pk, 1 tbg_sk_to_pk_ct, 2 tbg_sign, 3 tbg_sign_ct, 4
+// tbg_sum_pubkeys, 5 tbg_sum_sigs, 6 tbg_fast_aggregate_verify) as the engine makes it: work_size, then
+// work_bind over `base` (0: the sizing walk alone).  dims[4]: the signers' n, n_msgs, msg_bytes, tab_words; the
+// sums' n_sets, n_chunks, n_items / n_keys, msg_bytes.  secs[n][2]: offset, bytes of the sizing walk; ptrs[n]:
+// the description's pointers after the binding walk, in section order; *total: the allocation's bytes.
+// Returns the section count, -1 for an unknown call.
+int pl_work(uint32_t call, const uint64_t* dims, uint64_t base, uint64_t* total, uint64_t* secs, uint64_t* ptrs,
+            const char** names) {
+  auto run = [&](auto& w) {
+    const WorkWalk sized = work_size(w);
+    *total = sized.bytes();
+    for (uint32_t i = 0; i < sized.n; ++i) {
+      secs[2 * i] = sized.sec[i].off;
+      secs[2 * i + 1] = sized.sec[i].bytes;
+      names[i] = sized.sec[i].name;
+    }
+    if (base) work_bind(w, sized, (uint8_t*)(uintptr_t)base);
+    uint32_t i = 0;
+    auto read = [&](const char*, auto*& p, size_t, size_t = 0) { ptrs[i++] = (uint64_t)(uintptr_t)p; };
+    w.sections(read);
+    return (int)sized.n;
+  };
+  auto sum_dims = [&](SumWork& w, size_t part_elem) {
+    w.n_sets = dims[0];
+    w.n_chunks = dims[1];
+    w.part_elem = part_elem;
+  };
+  switch (call) {
+    case 0: {
+      SkToPkWork w;
+      w.n = dims[0];
+      return run(w);
+    }
+    case 1: {
+      SkToPkCtWork w;
+      w.n = dims[0];
+      w.tab_words = dims[3];
+      return run(w);
+    }
+    case 2: {
+      SignWork w;
+      w.n = dims[0];
+      w.n_msgs = dims[1];
+      w.msg_bytes = dims[2];
+      return run(w);
+    }
+    case 3: {
+      SignCtWork w;
+      w.n = dims[0];
+      w.n_msgs = dims[1];
+      w.msg_bytes = dims[2];
+      w.tab_words = dims[3];
+      return run(w);
+    }
+    case 4: {
+      SumPubkeysWork w;
+      sum_dims(w, sizeof(G1J));
+      w.n_items = dims[2];
+      return run(w);
+    }
+    case 5: {
+      SumSigsWork w;
+      sum_dims(w, sizeof(G2J));
+      w.n_items = dims[2];
+      return run(w);
+    }
+    case 6: {
+      FastAggVerifyWork w;
+      sum_dims(w, sizeof(G1J));
+      w.n_keys = dims[2];
+      w.msg_bytes = dims[3];
+      return run(w);
+    }
+  }
+  return -1;
+}
 
 }  // extern "C"

@@ -10,6 +10,12 @@ on the CPU, through the host twin tests/plan.
 4. The replay fit rule derived from the table against its closed form
    (tests/plan_mirror.py shape_fits) and the cases the GPU tests pin.
 5. l0_shape and sgb_plan against their Python mirrors.
+6. The workspaces of the one-shot calls (tbls_work.h): tests/golden/
+   oneshot_workspaces.json holds, for the smallest shapes that reach every
+   section rule, the bytes each call allocated and the bytes each of its
+   sections received while both were written by hand (recorded from the parent
+   commit by a host program that ran those lines as they stood); the
+   descriptions reproduce every section and never allocate more.
 """
 import ctypes
 import json
@@ -268,3 +274,64 @@ def test_sgb_plan_equals_its_mirror():
         assert (on, m.value) == plan_mirror.sgb_plan(rho), rho
     assert plan_mirror.sgb_plan(0) == (True, 1024) and plan_mirror.sgb_plan(1.25e-3) == (True, 128)
     assert not plan_mirror.sgb_plan(2e-2)[0]
+
+
+WORK_CALLS = ["tbg_sk_to_pk", "tbg_sk_to_pk_ct", "tbg_sign", "tbg_sign_ct", "tbg_sum_pubkeys", "tbg_sum_sigs",
+              "tbg_fast_aggregate_verify"]
+
+
+def work(call, dims, base=0):
+    """The C++ workspace of a one-shot call: (total bytes, [(name, offset, bytes, pointer)])."""
+    signer = call in WORK_CALLS[:4]
+    items = "n_keys" if call == "tbg_fast_aggregate_verify" else "n_items"
+    keys = ("n", "n_msgs", "msg_bytes", "tab_words") if signer else ("n_sets", "n_chunks", items, "msg_bytes")
+    d = np.array([dims.get(k, 0) for k in keys], dtype=np.uint64)
+    n_max = lib().pl_max_work_sections()
+    total = ctypes.c_uint64(0)
+    secs = np.zeros((n_max, 2), dtype=np.uint64)
+    ptrs = np.zeros(n_max, dtype=np.uint64)
+    names = (ctypes.c_char_p * n_max)()
+    n = lib().pl_work(WORK_CALLS.index(call), d.ctypes.data, base, ctypes.addressof(total), secs.ctypes.data,
+                      ptrs.ctypes.data, ctypes.addressof(names))
+    assert 0 < n <= n_max
+    return total.value, [(names[i].decode(), int(secs[i, 0]), int(secs[i, 1]), int(ptrs[i])) for i in range(n)]
+
+
+def test_oneshot_workspaces_equal_the_recorded_ones():
+    with open(os.path.join(HERE, "golden", "oneshot_workspaces.json")) as f:
+        rows = json.load(f)["rows"]
+    assert {r["call"] for r in rows} == set(WORK_CALLS)
+    # the shapes: signers n {1, 3} x messages {1, 2} x message bytes {0, 1, 33}; sums of 1 and 3 sets with an
+    # empty set, no item at all and a set of two chunks
+    for call in ("tbg_sign", "tbg_sign_ct"):
+        got = {(r["dims"]["n"], r["dims"]["n_msgs"], r["dims"]["msg_bytes"]) for r in rows if r["call"] == call}
+        assert got == {(n, m, b) for n in (1, 3) for m in (1, 2) for b in (0, 1, 33)}, call
+    for call in ("tbg_sk_to_pk", "tbg_sk_to_pk_ct"):
+        assert {r["dims"]["n"] for r in rows if r["call"] == call} == {1, 3}, call
+    for call in WORK_CALLS[4:]:
+        mine = [r["dims"] for r in rows if r["call"] == call]
+        items = "n_keys" if call == "tbg_fast_aggregate_verify" else "n_items"
+        assert {d["n_sets"] for d in mine} == {1, 3}, call
+        assert any(d[items] == 0 for d in mine) and any(d["n_chunks"] > d["n_sets"] for d in mine), call
+        assert any(0 < d["n_chunks"] < d["n_sets"] for d in mine), call  # an empty set among others
+    base = 0x7F0000001000
+    for r in rows:
+        label = (r["call"], r["dims"])
+        total, secs = work(r["call"], r["dims"])
+        assert len({name for name, *_ in secs}) == len(secs), label  # each section named once
+        end = 0
+        for name, off, nbytes, ptr in secs:
+            assert off % 16 == 0 and ptr == 0, (label, name)  # (the sizing walk hands out nothing)
+            assert off >= end, (label, name)                  # disjoint, in walk order
+            end = off + nbytes
+        assert end <= total, label
+        # the binding walk: the same sections at the same offsets, each pointer its section's address
+        total_b, bound = work(r["call"], r["dims"], base)
+        assert total_b == total and len(bound) == len(secs), label
+        for (name, off, nbytes, _), (name_b, off_b, nbytes_b, ptr) in zip(secs, bound):
+            assert (name_b, off_b, nbytes_b) == (name, off, nbytes) and ptr == base + off, (label, name)
+        # against the parent: every section what its sec() call received, the allocation never larger
+        assert [nbytes for _, _, nbytes, _ in secs] == r["sections"], label
+        assert total <= r["need"], label
+        if r["call"] != "tbg_fast_aggregate_verify":  # (whose sum reserved one 48-byte-per-set block it never carved)
+            assert total == r["need"], label
