@@ -21,6 +21,15 @@
 // operation, so each product or squaring swaps its operand once (for the
 // pair products) and one intermediate (for the xi term).
 //
+// The LINE step (hex_line_mul, most of a Miller kernel's work) is written
+// differently: each output component is one reduced sum of six products with
+// xi folded into the line operand, so it swaps no intermediate; the partner
+// view of a left operand carries the product's sign (hx_to_partner), the
+// line coefficients are whole on every lane, and the values of other hexad
+// lanes (A_{q+1}, the evaluated coefficients) come by ds_bpermute, one LDS
+// crossbar move per word and no VALU instruction, where a DPP trio exchange
+// costs two row shifts and one or two selects per word.
+//
 // The per-lane pieces are plain functions of (c, q, own, partner, ...) so
 // the host build checks the algebra by emulating the six lanes
 // (tests/hostcheck: hc_hex_*), against the tower and the trio.
@@ -96,6 +105,58 @@ TBG_HD Fp4h hx_comb2(uint32_t c, int q, const Fp4h& P, const Fp4h& Pn, const Fp4
 
 // ---- f * line, line = L0 + L2 x^2 with L0 = (l0, l4), L2 = l1 (evaluated):
 //   C_q = A_q L0 + (q < 2 ? y : 1) A_{q+1} l1   (quad_line_lane)
+// DIRECT form (the one the kernels run): each output component is ONE reduced
+// sum of three Fp2 products, six Fp products for lane c,
+//   C.a = A.a l0 + A.b (xi l4) + (q < 2 ? An.b (xi l1) : An.a l1)
+//   C.b = A.a l4 + A.b l0      + (q < 2 ? An.a l1      : An.b l1)
+// with xi folded into the LINE operand (two values per line, linear): 12
+// products and 2 reductions per lane (2,744 mads) against the Karatsuba
+// form's 10 and 5 (2,940), and none of its operand sums, W exchange, xi term,
+// fp_reduce or three of its REDC tails.  Both results are REDC outputs:
+// normalised, < 2p.
+//
+// Component c of X Y is x_c y0 +- x_(1-c) y1, minus on c = 0.  The sign rides
+// on the LEFT operand's partner view: lane c = 1 hands its partner the lazy
+// negation of its component (hx_to_partner), so the right operands are the
+// WHOLE line coefficient (y0, y1), the same on all six lanes -- no lane
+// selects components or signs of a line value, and nothing derived from one
+// has to be kept from the first sum to the second.  For xi Y the right pair
+// is (D, S), D = y0 - y1, S = y0 + y1 (normalised).
+// Bounds (TBG_BOUNDS_CHECK): the own views are < 2p, normalised; at most
+// three of the six left operands are fp_neg_l values (<= 16p, limbs < 2^29);
+// right operands normalised, < 18p (D), < 4p (S), < 2p (the rest), and an
+// fp_neg_l value only ever meets a y1 or an S: the sum of ratio products is
+// <= 3 * 2 * 18 + 3 * 16 * 4 = 300 < 2048, the columns 14 * 2^28 * (3 * 2^29 +
+// 3 * 2^28) + 14 * 2^56 + carry < 2^64 (fp_mul_sum's own check).
+TBG_HD Fp hx_to_partner(uint32_t c, const Fp& x) { return fp_select(c != 0, fp_neg_l(x), x); }
+// what trio lane s hands to lane s - 1 (its A is that lane's An): U enters
+// C.b, V enters C.a; (U, V) = (An.a, An.b) on the reading lanes q < 2 (s != 0),
+// (An.b, An.a) on q = 2 (s = 0)
+TBG_HD Fp hx_line_u_src(int s, const Fp4h& A) { return fp_select(s != 0, A.a, A.b); }
+TBG_HD Fp hx_line_v_src(int s, const Fp4h& A) { return fp_select(s != 0, A.b, A.a); }
+// (x0 y0 + x1 y1 + x2 y2)_c: the views' p as hx_to_partner gives it
+TBG_HD Fp hx_line_sum6(const Fp2o& x0, const Fp2& y0, const Fp2o& x1, const Fp2& y1, const Fp2o& x2, const Fp2& y2) {
+  TBG_BOUND(fp_ratio_p(x0.o) * fp_ratio_p(y0.c0) + fp_ratio_p(x0.p) * fp_ratio_p(y0.c1) +
+                    fp_ratio_p(x1.o) * fp_ratio_p(y1.c0) + fp_ratio_p(x1.p) * fp_ratio_p(y1.c1) +
+                    fp_ratio_p(x2.o) * fp_ratio_p(y2.c0) + fp_ratio_p(x2.p) * fp_ratio_p(y2.c1) < 2048.0,
+            "hx_line_sum6 bound");
+  const Fp* const L[6] = {&x0.o, &x0.p, &x1.o, &x1.p, &x2.o, &x2.p};
+  const Fp* const R[6] = {&y0.c0, &y0.c1, &y1.c0, &y1.c1, &y2.c0, &y2.c1};
+  return fp_mul_sum<6>(L, R);
+}
+TBG_HD Fp2 hx_line_xi(const Fp2& y) { return {fp_sub(y.c0, y.c1), fp_add(y.c0, y.c1)}; }
+// C.b and C.a on lane q of the trio (either component: the views carry it)
+TBG_HD Fp hx_line_cb(const Fp4o& A, const Fp2o& U, const Fp2& l0, const Fp2& l1, const Fp2& l4) {
+  return hx_line_sum6(A.a, l4, A.b, l0, U, l1);
+}
+TBG_HD Fp hx_line_ca(int q, const Fp4o& A, const Fp2o& V, const Fp2& l0, const Fp2& l1, const Fp2& l4) {
+  const Fp2 x1 = hx_line_xi(l1);
+  return hx_line_sum6(A.a, l0, A.b, hx_line_xi(l4), V, {fp_select(q < 2, x1.c0, l1.c0), fp_select(q < 2, x1.c1, l1.c1)});
+}
+
+// The KARATSUBA form of the same product, five REDC(ab + cd) per lane in two
+// phases around one exchange: the reference the direct form is checked
+// against (tests/hostcheck hc_hex_line; no kernel runs it).
 // phase 1: the five products' components and W, the value whose xi multiple
 // enters C.a (t1, plus u.b on lanes 0, 1)
 struct HxLine { Fp t0, t1, s, ua, ub, W; };
@@ -237,32 +298,62 @@ TBG_DEV Fp4h hex_sqr(const Fp4h& A) {
   return hx_comb2(c, q, P, Pn, Pp, T, V, hx_swap(V));
 }
 
-// f * (l0, l1, l4) in the order that keeps the live set small: the two
-// A_{q+1} l1 products first (A_{q+1}'s partner components by a swap of the
-// exchanged own ones), then A_q (l0, l4) with l0 loaded only then
-// (`l0_src`: the line's first 2 NL words, or null with l0 given)
-TBG_DEV Fp4h hex_line_mul(const Fp4h& A, const uint32_t* l0_src, Fp2o l0, const Fp2o& l1, const Fp2o& l4) {
+// The value of wave lane `addr / 4` on every lane that asks for it: one
+// ds_bpermute per word (the LDS crossbar, no LDS memory, no VALU slot), for
+// the exchanges a DPP row shift cannot do in one move: a trio lane's value
+// takes two shifts and a select per word (xch, bls_quad.h), a broadcast two
+// shifts and two selects, and the component partner's a ds_swizzle on top.
+// A hexad reads its own six lanes only, which run together.
+TBG_DEV Fp hx_from(uint32_t addr, const Fp& x) {
+  Fp r;
+#pragma unroll
+  for (int i = 0; i < NL; ++i) r.l[i] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)addr, (int)x.l[i]);
+  return r;
+}
+// Byte addresses for hx_from: lane (0, 0) of this thread's hexad and this
+// lane's A_{q+1} source, lane ((q + 1) % 3, c).  Formed from an OPAQUE thread
+// index where a step asks for them: loop invariants otherwise, and the six
+// addresses of a line step hoisted out of the Miller loop are held across
+// hex_sqr, the kernels' register peak.  Scratch bytes / spilled VGPRs with
+// the addresses plain -> opaque: k_miller_hex<MILLER_L0>
+// and <MILLER_GROUPS> 32 / 7 -> 16 / 3, k_l0m_miller 12 / 2 -> 0,
+// k_rlc_gident_miller 8 / 1 -> 0.
+struct HxLanes { uint32_t lead, next; };
+TBG_DEV HxLanes hx_lanes() {
+  uint32_t t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  const uint32_t q = (t & 15u) % 3u, lead = ((t - q) & 47u) << 2;  // (& 63 & ~16)
+  return {lead, lead + (((q == 2u ? 0u : q + 1u) + (t & 16u)) << 2)};
+}
+TBG_DEV uint32_t hx_lane_addr(uint32_t lead, uint32_t q, uint32_t c) { return lead + ((q + 16u * c) << 2); }
+
+// f * (l0, l1, l4), the line coefficients whole on every lane, in the order
+// that keeps the live set small: C.b, then C.a; A_{q+1}'s U / V
+// (hx_line_u_src: selected on the lane that holds them, so one select per
+// word serves every reader) fetched just before the sum they enter; l0 loaded
+// only then (`l0_src`: the line's first 2 NL words)
+TBG_DEV Fp4h hex_line_mul(const Fp4h& A, const uint32_t* l0_src, const Fp2& l1, const Fp2& l4) {
   const uint32_t c = hex_c();
   const int q = quad_lane();
-  HxLine r;
-  {
-    const Fp4h An = hxch<QP_NEXT>(A);
-    hx_line_u(c, hx_own_par(An, hx_swap(An)), l1, r);
-  }
-  if (l0_src) {
+  const uint32_t own = hx_lanes().next, par = own ^ 64u;
+  const Fp4o Av = hx_own_par(A, hx_swap(Fp4h{hx_to_partner(c, A.a), hx_to_partner(c, A.b)}));
+  const Fp U = hx_line_u_src(q, A);
+  Fp2 l0;
 #pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      l0.o.l[i] = l0_src[c * NL + i];
-      l0.p.l[i] = l0_src[(c ^ 1u) * NL + i];
-    }
+  for (int i = 0; i < NL; ++i) {
+    l0.c0.l[i] = l0_src[i];
+    l0.c1.l[i] = l0_src[NL + i];
   }
-  hx_line_t(c, q, hx_own_par(A, hx_swap(A)), l0, l4, r);
-  return hx_line2(c, q, r, hx_swap(r.W));
+  Fp4h C;
+  C.b = hx_line_cb(Av, Fp2o{hx_from(own, U), hx_from(par, hx_to_partner(c, U))}, l0, l1, l4);
+  const Fp V = hx_line_v_src(q, A);  // (formed only now: nothing of it is live over C.b's sum)
+  C.a = hx_line_ca(q, Av, Fp2o{hx_from(own, V), hx_from(par, hx_to_partner(c, V))}, l0, l1, l4);
+  return C;
 }
 
 // f *= line(idx) of stored (unevaluated) lines at affine P = (-x, y): lane
-// (0, c) evaluates l1_c (-x), lane (1, c) l4_c y; the trio broadcasts them
-// and the pair swaps the other components.  `v` is this lane's operand:
+// (0, c) evaluates l1_c (-x), lane (1, c) l4_c y, and every lane of the hexad
+// reads the four products from there.  `v` is this lane's operand:
 // -x on q = 0, y on q = 1 (q = 2: any, its product is not used).
 TBG_DEV Fp4h hex_line_at_v(const Fp4h& A, const uint32_t* lines, int idx, const Fp& v) {
   const uint32_t c = hex_c();
@@ -273,8 +364,10 @@ TBG_DEV Fp4h hex_line_at_v(const Fp4h& A, const uint32_t* lines, int idx, const 
 #pragma unroll
   for (int i = 0; i < NL; ++i) lk.l[i] = src[(k + (int)c) * NL + i];
   const Fp e = fp_mul(lk, v);
-  const Fp e1 = xch<QP_B0>(e), e4 = xch<QP_B1>(e);
-  return hex_line_mul(A, src, Fp2o{}, Fp2o{e1, hx_swap(e1)}, Fp2o{e4, hx_swap(e4)});
+  const uint32_t lead = hx_lanes().lead;
+  const Fp2 l1 = {hx_from(hx_lane_addr(lead, 0, 0), e), hx_from(hx_lane_addr(lead, 0, 1), e)};
+  const Fp2 l4 = {hx_from(hx_lane_addr(lead, 1, 0), e), hx_from(hx_lane_addr(lead, 1, 1), e)};
+  return hex_line_mul(A, src, l1, l4);
 }
 TBG_DEV Fp4h hex_line_at(const Fp4h& A, const uint32_t* lines, int idx, const Fp& nx, const Fp& y) {
   return hex_line_at_v(A, lines, idx, fp_select(quad_lane() == 0, nx, y));
@@ -283,17 +376,16 @@ TBG_DEV Fp4h hex_line_at(const Fp4h& A, const uint32_t* lines, int idx, const Fp
 TBG_DEV Fp hex_line_operand(const G1A& P) { return quad_lane() == 0 ? P.x : P.y; }
 // f *= line(idx) of folded (already evaluated) lines
 TBG_DEV Fp4h hex_line_folded(const Fp4h& A, const uint32_t* lines, int idx) {
-  const uint32_t c = hex_c();
   const uint32_t* src = lines + LINE_WORDS * idx;
-  Fp2o l[3];
+  Fp2 l[2];
 #pragma unroll
-  for (int k = 0; k < 3; ++k)
+  for (int k = 0; k < 2; ++k)
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
-      l[k].o.l[i] = src[(2 * k + (int)c) * NL + i];
-      l[k].p.l[i] = src[(2 * k + (int)(c ^ 1u)) * NL + i];
+      l[k].c0.l[i] = src[(2 * k + 2) * NL + i];
+      l[k].c1.l[i] = src[(2 * k + 3) * NL + i];
     }
-  return hex_line_mul(A, nullptr, l[0], l[1], l[2]);
+  return hex_line_mul(A, src, l[0], l[1]);
 }
 
 // x y (quad_mul_in on the hexad)
@@ -398,6 +490,22 @@ TBG_DEV Fp4h hex_load(const uint32_t* src) {
 TBG_DEV void hex_store(uint32_t* dst, const Fp4h& A) {
   const int q = quad_lane();
   const uint32_t c = hex_c();
+#pragma unroll
+  for (int j = 0; j < NL; ++j) {
+    dst[4 * NL * q + c * NL + j] = A.a.l[j];
+    dst[4 * NL * q + (2 + c) * NL + j] = A.b.l[j];
+  }
+}
+
+// hex_store as a kernel's last statement after a long loop: the lane roles
+// are formed again from an opaque thread index, so q is not held (or spilled)
+// across the loop for the sake of this address.  k_miller_hex<MILLER_L0> and
+// <MILLER_GROUPS> go from 16 B of scratch (3 VGPRs spilled, q among them) to
+// none with it; k_l0m_miller has none with hex_store and keeps it.
+TBG_DEV void hex_store_late(uint32_t* dst, const Fp4h& A) {
+  uint32_t t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  const uint32_t q = (t & 15u) % 3u, c = (t >> 4) & 1u;
 #pragma unroll
   for (int j = 0; j < NL; ++j) {
     dst[4 * NL * q + c * NL + j] = A.a.l[j];

@@ -107,7 +107,7 @@ __global__ void TBG_LAUNCH_N(TBG_HEX_WAVES) k_miller_hex(DevBatch B) {
       }
     }
   }
-  hex_store(dst, f);
+  hex_store_late(dst, f);
 }
 
 void launch_l0_miller_hex(const DevBatch& B, hipStream_t st) {

@@ -82,8 +82,28 @@ def main():
     rlc_partial, _ = measure(lib.hc_stage_rlc_partial, 0x9E3779B97F4A7C15)
     duty_sum4, _ = measure(lib.hc_stage_duty_sum, 4)
     group_lines8, _ = measure(lib.hc_stage_group_lines, G)
-    chunk2, _ = measure(lib.hc_stage_miller_chunk, C, 0)
-    chunk2f, _ = measure(lib.hc_stage_miller_chunk, C, 1)
+    # hc_stage_miller_chunk forms its line products as the trio does (quad_line_lane, the Karatsuba
+    # form: five REDC(ab + cd) per hexad lane); the kernels run the hexad's direct form (bls_hex.h
+    # hex_line_mul: two fp_mul_sum<6> per lane).  Probe: tests/hexline/hexline_host.cpp built with
+    # TBG_COUNT_OPS counts one line product over the six lanes in either form; every line product of a
+    # measured chunk is corrected by the difference (miller_chunk below: 68 lines per duty pair and for
+    # the folded S).
+    xsrc = os.path.join(ROOT, "tests", "hexline", "hexline_host.cpp")
+    xlib_path = os.path.join(ROOT, "tests", "hexline", "libhexline_count.so")
+    subprocess.check_call(["/opt/rocm/llvm/bin/clang++", "-O1", "-std=c++17", "-fPIC", "-shared", "-DTBG_COUNT_OPS",
+                           "-Wno-pass-failed", xsrc, "-o", xlib_path])
+    xlib = ctypes.CDLL(xlib_path)
+    xlib.hxl_hc_count.restype = ctypes.c_ulonglong
+    line_direct, line_kara = xlib.hxl_hc_count(0), xlib.hxl_hc_count(1)
+    assert line_direct == 6 * 2 * 7 * 196 and line_kara - line_direct == 6 * (196 + 2 * 14), (line_direct, line_kara)
+    line_delta = line_kara - line_direct  # 224 per lane and line: one product's 196, two fp_reduce at 14
+
+    def miller_chunk(pairs, folded):
+        """hc_stage_miller_chunk with its 68 * (pairs + folded) line products in the direct form."""
+        n, _ = measure(lib.hc_stage_miller_chunk, pairs, folded)
+        return n - 68 * (pairs + folded) * line_delta
+    chunk2 = miller_chunk(C, 0)
+    chunk2f = miller_chunk(C, 1)
     final4, _ = measure(lib.hc_stage_group_final, G // C)
     rlc_check_per_group = chunk2f + (G // C - 1) * chunk2 + final4
     # Level 0 (k_msm.hip): per partial the G1 table product and 4 bucket
@@ -103,13 +123,13 @@ def main():
     g2_add, _ = measure(lib.hc_stage_g2_add)
     final1, _ = measure(lib.hc_stage_group_final, 1)
     qmul = measure(lib.hc_stage_group_final, 2)[0] - final1
-    s_quad, _ = measure(lib.hc_stage_miller_chunk, 0, 1)
+    s_quad = miller_chunk(0, 1)
     nch = G // C
     # a P-chunk hexad of c duties costs base + c * per_duty (62 squarings, 68
     # line products per duty): the level-0 launch shape (G, C) varies with the
     # launch size (tbls_plan.h l0_shape), so the kernels' models are per
     # chunk and per duty
-    chunk8, _ = measure(lib.hc_stage_miller_chunk, 8, 0)
+    chunk8 = miller_chunk(8, 0)
     chunk_per_duty = (chunk8 - chunk2) / 4
     chunk_base = chunk2 - 4 * chunk_per_duty
     # per-kernel probes (one item of each kernel of the level-0 chain)

@@ -22,6 +22,22 @@ __global__ void __launch_bounds__(64, 2) k_isa_line_folded(uint32_t* io, const u
   f = hex_line_folded(f, lines, 0);
   hex_store(io, f);
 }
+// the line steps as the Miller kernels run them: a rolled loop of steps
+// alone, f and the operand live across it (compile with the Miller unit's
+// -mllvm -amdgpu-sched-strategy=max-ilp to count what k_miller_hex gets)
+__global__ void __launch_bounds__(64, 2) k_isa_line_at_v_loop(uint32_t* io, const uint32_t* lines, const G1A* P, int n) {
+  Fp4h f = hex_load(io);
+  const Fp v = hex_line_operand(*P);
+#pragma unroll 1
+  for (int i = 0; i < n; ++i) f = hex_line_at_v(f, lines, i, v);
+  hex_store(io, f);
+}
+__global__ void __launch_bounds__(64, 2) k_isa_line_folded_loop(uint32_t* io, const uint32_t* lines, int n) {
+  Fp4h f = hex_load(io);
+#pragma unroll 1
+  for (int i = 0; i < n; ++i) f = hex_line_folded(f, lines, i);
+  hex_store(io, f);
+}
 __global__ void __launch_bounds__(64, 2) k_isa_pair_mul(uint32_t* io) {
   Fp a, ap, b, bp;
   for (int i = 0; i < NL; ++i) { a.l[i] = io[i]; ap.l[i] = io[NL + i]; b.l[i] = io[2 * NL + i]; bp.l[i] = io[3 * NL + i]; }
