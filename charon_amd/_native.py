@@ -311,6 +311,10 @@ SIGNATURES = {
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "tbg_fast_aggregate_verify": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # commit48, poly_first, n_polys, eval_poly, eval_id, n_evals, out48, eval_status, commit_status (optional)
+    "tbg_eval_commitments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p]),
     # include/tbls_ssz.h (host code)
     "tbg_ssz_size": (ctypes.c_uint32, [ctypes.c_uint32]),
     "tbg_ssz_roots": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_void_p,

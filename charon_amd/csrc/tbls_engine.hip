@@ -1829,4 +1829,52 @@ int tbg_fast_aggregate_verify(tbg_ctx* c, const uint32_t* pubkey_ids, const uint
   return cs.drain(rc);
 }
 
+// ---- Feldman commitment polynomials (k_feldman.hip, bls_feldman.h) ---------
+// tbls/tss.go:95-116 (NewTSS), :293-325 (getPubShare): the pubshares from the
+// verifier alone; at one identifier, the public side of Feldman share verification.
+int tbg_eval_commitments(tbg_ctx* c, const uint8_t* commit48, const uint32_t* poly_first, uint32_t n_polys,
+                         const uint32_t* eval_poly, const uint32_t* eval_id, uint32_t n_evals, uint8_t* out48,
+                         int32_t* eval_status, int32_t* commit_status) {
+  if (!c) return TBG_E_INVALID_ARG;
+  if (n_polys) {
+    if (!commit48 || !poly_first || poly_first[0] != 0) return TBG_E_INVALID_ARG;
+    for (uint32_t p = 0; p < n_polys; ++p)
+      if (poly_first[p + 1] <= poly_first[p]) return TBG_E_INVALID_ARG;  // decreasing, or an empty polynomial
+  }
+  if (n_evals) {
+    if (!eval_poly || !eval_id || !out48 || !eval_status) return TBG_E_INVALID_ARG;
+    for (uint32_t e = 0; e < n_evals; ++e)
+      if (eval_poly[e] >= n_polys) return TBG_E_INVALID_ARG;
+  }
+  if (n_polys == 0 || n_evals == 0) return TBG_OK;
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  const uint32_t nc = poly_first[n_polys];
+  EvalCommitWork w;
+  w.n_commits = nc;
+  w.n_polys = n_polys;
+  w.n_evals = n_evals;
+  CallScope cs(c->stream);
+  int rc = cs.open(w);
+  if (rc != TBG_OK) return rc;
+  hipStream_t st = c->stream;
+  if (hipMemcpyAsync(w.commit48, commit48, 48ull * nc, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(w.poly_first, poly_first, 4ull * (n_polys + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(w.eval_poly, eval_poly, 4ull * n_evals, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(w.eval_id, eval_id, 4ull * n_evals, hipMemcpyHostToDevice, st) != hipSuccess)
+    rc = TBG_E_DEVICE;
+  if (rc == TBG_OK) {
+    tbg::launch_decode_pubkeys(w.commit48, nc, w.t_c, w.t_xc, w.commit_status, st);
+    tbg::launch_fv_eval(w.t_c, w.commit_status, nc, w.poly_first, n_polys, w.eval_poly, w.eval_id, n_evals, w.out48,
+                        w.eval_status, st);
+    if (hipGetLastError() != hipSuccess) rc = TBG_E_DEVICE;
+  }
+  if (rc == TBG_OK &&
+      (hipMemcpyAsync(out48, w.out48, 48ull * n_evals, hipMemcpyDeviceToHost, st) != hipSuccess ||
+       hipMemcpyAsync(eval_status, w.eval_status, 4ull * n_evals, hipMemcpyDeviceToHost, st) != hipSuccess ||
+       (commit_status && hipMemcpyAsync(commit_status, w.commit_status, 4ull * nc, hipMemcpyDeviceToHost, st) != hipSuccess)))
+    rc = TBG_E_DEVICE;
+  return cs.drain(rc);
+}
+
 }  // extern "C"

@@ -598,5 +598,10 @@ void launch_sk_to_pk_ct(const uint8_t* sk32, uint32_t n, const uint32_t* tab, ui
                         hipStream_t st);
 void launch_sign_ct(const uint8_t* sk32, const uint32_t* item_msg, uint32_t n, uint32_t n_msgs, const uint32_t* tab,
                     const int32_t* h_status, uint8_t* sig96, int32_t* status, hipStream_t st);
+// Feldman commitment polynomials (k_feldman.hip, bls_feldman.h): evaluation e is polynomial
+// eval_poly[e] -- the decoded commitments [poly_first[p], poly_first[p + 1]) of tab[n_commits] -- at eval_id[e]
+void launch_fv_eval(const G1A* tab, const int32_t* tab_status, uint32_t n_commits, const uint32_t* poly_first,
+                    uint32_t n_polys, const uint32_t* eval_poly, const uint32_t* eval_id, uint32_t n_evals, uint8_t* out48,
+                    int32_t* status, hipStream_t st);
 
 }  // namespace tbg

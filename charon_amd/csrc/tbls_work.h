@@ -1,6 +1,6 @@
 // The workspace of every call that runs to completion inside itself --
-// tbg_sk_to_pk, tbg_sign, their hardened forms, the plain sums and
-// tbg_fast_aggregate_verify: one struct per call whose sections() names every
+// tbg_sk_to_pk, tbg_sign, their hardened forms, the plain sums,
+// tbg_fast_aggregate_verify and tbg_eval_commitments: one struct per call whose sections() names every
 // section of the call's single device allocation once, with its element type
 // and count, in arena order.  The size comes from one walk of it with a null
 // base and the pointers from a second walk over the allocation (work_size,
@@ -199,6 +199,31 @@ struct FastAggVerifyWork : SumWork {
     v("part_list", part_list, n);
     v("partial_status", partial_status, n);
     v("duty_status", duty_status, n);
+  }
+};
+
+// tbg_eval_commitments: n_commits Feldman commitments in n_polys polynomials,
+// their decoded table (t_xc: the decode kernel's second output, unused
+// here), then n_evals evaluations.
+struct EvalCommitWork {
+  size_t n_commits = 0, n_polys = 0, n_evals = 0;
+  uint8_t* commit48 = nullptr;
+  uint32_t *poly_first = nullptr, *eval_poly = nullptr, *eval_id = nullptr;
+  G1A *t_c = nullptr, *t_xc = nullptr;
+  int32_t* commit_status = nullptr;
+  uint8_t* out48 = nullptr;
+  int32_t* eval_status = nullptr;
+  template <class V>
+  void sections(V& v) {
+    v("commit48", commit48, 48 * n_commits);
+    v("poly_first", poly_first, n_polys + 1);
+    v("eval_poly", eval_poly, n_evals);
+    v("eval_id", eval_id, n_evals);
+    v("t_c", t_c, n_commits);
+    v("t_xc", t_xc, n_commits);
+    v("commit_status", commit_status, n_commits);
+    v("out48", out48, 48 * n_evals);
+    v("eval_status", eval_status, n_evals);
   }
 };
 

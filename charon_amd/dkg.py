@@ -263,7 +263,7 @@ def agg_sign_lock_hash(share_lists, lock_hash: bytes, engine=None) -> bytes:
     return bytes(agg[0])
 
 
-def create_cluster_tss(secrets, t: int, n: int, rng, engine=None, hardened=False):
+def create_cluster_tss(secrets, t: int, n: int, rng, engine=None, hardened=False, from_commitments=False):
     """getTSSShares of `charon create cluster` (cmd/createcluster.go:250-270):
     every validator secret split t-of-n and its TSS.  One split on the host
     (integers), ONE sk_to_pk launch for every commitment and every pubshare
@@ -275,7 +275,15 @@ def create_cluster_tss(secrets, t: int, n: int, rng, engine=None, hardened=False
     production keys (tbls.split_secret).  hardened=True forms every commitment
     and pubshare on the fixed schedule (tbg_sk_to_pk_ct; a zero or out-of-range
     scalar raises); the split itself stays on host integers and keeps the
-    warning -- the product's caller is Go, which splits in kryptology."""
+    warning -- the product's caller is Go, which splits in kryptology.
+
+    from_commitments=True derives the pubshares the way NewTSS does: the
+    scalar-multiplication launch forms the V*t commitments only (hardened or
+    not as above), ONE Engine.eval_commitments launch evaluates them at
+    1..n for all V*n pubshares, and no share value reaches the device.  Same
+    return value, errors and residency.  Off by default: at large thresholds
+    (170-of-255) Horner's rule over the commitments needs more group
+    operations than one 256-bit ladder per share."""
     e = tbls._engine(engine)
     splits, polys = [], []
     for s in secrets:
@@ -284,10 +292,22 @@ def create_cluster_tss(secrets, t: int, n: int, rng, engine=None, hardened=False
         polys.append(poly)
     if not splits:
         return [], []
-    scalars = [c for p in polys for c in p] + [s.value for sh in splits for s in sh]
-    pks = tbls._sk_to_pk(scalars, e, hardened, "unmarshal secret")
     nd = len(polys)
-    commits, shares48 = pks[:nd * t], pks[nd * t:]
+    if from_commitments:
+        commits = tbls._sk_to_pk([c for p in polys for c in p], e, hardened, "unmarshal secret")
+        if hardened and any(s.value == 0 for sh in splits for s in sh):  # (what the fixed-schedule ladder refuses)
+            raise tbls.TblsError("unmarshal secret: " + tbls._KS_ERRORS[eng.KS_ZERO])
+        shares48 = []
+        ids = list(range(1, n + 1))
+        for pks, st, cst in tbls._eval_verifiers([commits[d * t:(d + 1) * t] for d in range(nd)], [ids] * nd, e):
+            for pk, s in zip(pks, st):
+                if s not in (eng.FV_OK, eng.FV_IDENTITY):  # (an identity pubshare is refused below, as without the keyword)
+                    raise tbls._fv_error(s, cst)
+                shares48.append(bytes(pk))
+    else:
+        scalars = [c for p in polys for c in p] + [s.value for sh in splits for s in sh]
+        pks = tbls._sk_to_pk(scalars, e, hardened, "unmarshal secret")
+        commits, shares48 = pks[:nd * t], pks[nd * t:]
     keys = tbls.key_from_bytes_batch(shares48, e)
     dvs = []
     for d in range(nd):

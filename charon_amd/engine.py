@@ -26,6 +26,8 @@ DS_AGG_INVALID, DS_AGG_PUBKEY = -26, -27  # OP_AGGREGATE_VERIFY: the aggregate's
 SS_ERROR, SS_INVALID, SS_VALID = 30, 31, 32
 # per-item status of the hardened signer (TBG_KS_*, sk_to_pk_ct / sign_ct)
 KS_OK, KS_ZERO, KS_RANGE, KS_MSG = 0, -40, -41, -42
+# per-evaluation status of eval_commitments (TBG_FV_*), in their precedence
+FV_OK, FV_ID, FV_COMMIT, FV_KEY_IDENTITY, FV_IDENTITY = 0, -50, -51, -52, -53
 OP_VERIFY, OP_AGGREGATE, OP_VERIFY_AGGREGATE = 1, 2, 3
 # aggregate every duty, then CoreVerify the aggregate under the duty's group key, in one
 # launch: pubkey_ids holds one resident id per DUTY
@@ -448,6 +450,27 @@ class Engine:
         self._check(self._lib.tbg_fast_aggregate_verify(self._h, _ptr(ids), _ptr(koff), n, _ptr(data), _ptr(moff),
                                                         _ptr(a), _ptr(st)), "tbg_fast_aggregate_verify")
         return st
+
+    # ---- Feldman commitment polynomials (tbls.NewTSS, share verification) ----
+    def eval_commitments(self, commits, poly_first, eval_poly, eval_id):
+        """tbg_eval_commitments: polynomial p owns the 48-byte commitments
+        [poly_first[p], poly_first[p + 1]), lowest coefficient first; evaluation e
+        is polynomial eval_poly[e] at the identifier eval_id[e] -> (out [n, 48],
+        eval_status [n] of FV_*, commit_status per commitment: 0, 1 for the
+        identity, or a PS_ERR_* decode code)."""
+        pf, ep, ei = _u32(poly_first), _u32(eval_poly), _u32(eval_id)
+        if len(ep) != len(ei):
+            raise ValueError("eval_poly and eval_id must have the same length")
+        n_polys, n = max(len(pf) - 1, 0), len(ep)
+        a = _u8(commits, 48) if len(commits) else np.zeros((0, 48), np.uint8)
+        if n_polys and int(pf[-1]) != a.shape[0]:
+            raise ValueError("poly_first must end at the number of commitments")
+        out = np.zeros((n, 48), dtype=np.uint8)
+        st = np.zeros(n, dtype=np.int32)
+        cst = np.zeros(a.shape[0], dtype=np.int32)
+        self._check(self._lib.tbg_eval_commitments(self._h, _ptr(a), _ptr(pf), n_polys, _ptr(ep), _ptr(ei), n, _ptr(out),
+                                                   _ptr(st), _ptr(cst)), "tbg_eval_commitments")
+        return out, st, cst
 
 
 class MultiEngine:

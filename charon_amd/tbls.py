@@ -8,6 +8,7 @@ parity test reads like ``tbls/tss_test.go``:
   aggregate(partial_sigs) -> Signature                 tss.go:142-149
   verify_and_aggregate(tss, partial_sigs, msg)         tss.go:153-187
   TSS(pubshares, num_shares, threshold, public_key)    tss.go:62-116
+  new_tss(commitments, num_shares) -> TSS              tss.go:95-116, 293-325 (NewTSS, getPubShare)
   split_secret / combine_shares / generate_tss         tss.go:256-290, 220-253, 120-139
   sign / partial_sign (test-only, not side-channel safe unless
   hardened=True)                                        tss.go:200-217
@@ -18,6 +19,8 @@ plus the batch entry points the batch-aware call sites use:
   verify_and_aggregate_batch(duties) -> list[(Signature, signers) | TblsError]
   aggregate_batch(duties) -> list[Signature | TblsError]
   aggregate_and_verify_batch(duties) -> list[Signature | TblsError]
+  new_tss_batch(verifiers, n) / pubshares_from_commitments_batch(verifiers, n)
+  feldman_verify_batch(items) -> list[bool | TblsError]
 
 and the hardened signer (tbg_sign_ct / tbg_sk_to_pk_ct: fixed-schedule scalar
 multiplication, key material wiped), for the keys of a create-cluster or DKG
@@ -472,11 +475,11 @@ def _sk_to_pk(scalars, engine, hardened, what):
 def tss_from_shares(shares, commits, engine=None, hardened=False) -> TSS:
     """The TSS of a split whose scalar shares are at hand: pubshare i is
     sk_to_pk(f(i)) (what NewTSS's sum over the commitments evaluates to), the
-    group key is C_0 and the threshold is the number of commitments.  Only
-    for callers that hold the shares (GenerateTSS, create cluster): deriving
-    the pubshares from the commitments alone (tbls.NewTSS proper) is not
-    implemented.  Test-only scalar multiplication unless hardened, see
-    split_secret."""
+    group key is C_0 and the threshold is the number of commitments.  For
+    callers that hold the shares (GenerateTSS, create cluster); a caller with
+    the commitments alone uses new_tss (tbls.NewTSS proper), which reaches
+    the same pubshares without any share.  Test-only scalar multiplication
+    unless hardened, see split_secret."""
     shares = list(shares)
     commits = [bytes(c) for c in commits]
     pks = _sk_to_pk([s.value for s in shares], engine, hardened, "unmarshal secret")
@@ -489,6 +492,124 @@ def tss_from_shares(shares, commits, engine=None, hardened=False) -> TSS:
             raise TblsError("unmarshal pubshare: " + _PK_ERRORS[1])
         pub[s.identifier] = PublicKey(bytes(pk))
     return TSS(pub, len(shares), len(commits), PublicKey(commits[0]), tuple(commits))
+
+
+# ---- tbls.NewTSS: the TSS from the Feldman verifier alone (tss.go:95-116, getPubShare :293-325)
+_IDENT48 = bytes([0xC0]) + bytes(47)
+
+
+def _verifier_bytes(commitments):
+    """The 48-byte encodings of one verifier's commitments (PublicKey or bytes each)."""
+    cs = [_raw(c, PublicKey) for c in commitments]
+    if not cs:
+        raise TblsError("new TSS: the verifier has no commitments")
+    for c in cs:
+        if len(c) != 48:
+            raise TblsError("unmarshal pubkey: invalid length")
+    return cs
+
+
+def _eval_verifiers(verifiers, ids, e):
+    """ONE Engine.eval_commitments launch: verifier v at every identifier of
+    ids[v].  Per verifier returns (outputs, eval statuses, commitment statuses)."""
+    first = np.concatenate([[0], np.cumsum([len(v) for v in verifiers])]).astype(np.uint32)
+    eval_poly = [v for v, iv in enumerate(ids) for _ in iv]
+    out, st, cst = e.eval_commitments(b"".join(c for v in verifiers for c in v), first, eval_poly,
+                                      [i for iv in ids for i in iv])
+    res, k = [], 0
+    for v, iv in enumerate(ids):
+        res.append((out[k:k + len(iv)], st[k:k + len(iv)].tolist(), cst[first[v]:first[v + 1]].tolist()))
+        k += len(iv)
+    return res
+
+
+def _fv_error(st, commit_status):
+    """The TblsError of a failed evaluation (FV_*), the strings of NewTSS."""
+    if st == eng.FV_COMMIT:
+        code = next(c for c in commit_status if c not in (0, 1))
+        return TblsError("unmarshal commitment: " + _PK_ERRORS.get(code, str(code)))
+    if st == eng.FV_KEY_IDENTITY:
+        return TblsError("unmarshal pubkey: " + _PK_ERRORS[1])
+    if st == eng.FV_IDENTITY:
+        return TblsError("unmarshal pubshare: " + _PK_ERRORS[1])
+    return TblsError("share identifier must be 1..255" if st == eng.FV_ID else f"evaluate commitments: status {st}")
+
+
+def pubshares_from_commitments_batch(verifiers, num_shares: int, engine=None):
+    """getPubShare (tss.go:293-325) for every identifier 1..num_shares of every
+    verifier, in ONE launch: pubshare_i = C_0 + [i] C_1 + ... + [i^(t-1)] C_(t-1)
+    from the t commitments alone -- no share, and no secret, is needed or
+    touched.  Per verifier returns the list of 48-byte pubshares, or the
+    TblsError of new_tss for the first failing identifier."""
+    verifiers = [_verifier_bytes(v) for v in verifiers]
+    if not 1 <= int(num_shares) <= 255:
+        raise TblsError("new TSS: need 1 <= num_shares <= 255")
+    if not verifiers:
+        return []
+    ids = list(range(1, int(num_shares) + 1))
+    out = []
+    for pks, st, cst in _eval_verifiers(verifiers, [ids] * len(verifiers), _engine(engine)):
+        bad = next((s for s in st if s != eng.FV_OK), None)
+        out.append([bytes(pk) for pk in pks] if bad is None else _fv_error(bad, cst))
+    return out
+
+
+def new_tss_batch(verifiers, num_shares: int, engine=None):
+    """new_tss for many verifiers in ONE launch: a TSS per verifier, or its TblsError."""
+    verifiers = [_verifier_bytes(v) for v in verifiers]
+    out = []
+    for cs, r in zip(verifiers, pubshares_from_commitments_batch(verifiers, num_shares, engine)):
+        if isinstance(r, Exception):
+            out.append(r)
+        else:
+            out.append(TSS({i + 1: PublicKey(pk) for i, pk in enumerate(r)}, int(num_shares), len(cs), PublicKey(cs[0]),
+                           tuple(cs)))
+    return out
+
+
+def new_tss(commitments, num_shares: int, engine=None) -> TSS:
+    """tbls.NewTSS (tss.go:95-116): the TSS of a Feldman verifier -- the t
+    commitments C_j = [a_j] g1, 48 bytes each, lowest coefficient first.  The
+    threshold is their number, the group key is C_0 and pubshare i is the
+    commitment polynomial evaluated at i on the GPU (Engine.eval_commitments).
+    Raises as the reference does, for the first failing i in the order 1..n:
+    "unmarshal pubkey: public key is the identity" when C_0 is the identity,
+    "unmarshal pubshare: public key is the identity" when a pubshare is.  Go
+    receives the verifier as decoded points; here it arrives as bytes, so a
+    commitment that does not decode raises "unmarshal commitment: ..." with
+    key_from_bytes_batch's reason -- that string is this project's own.  A
+    commitment of another length raises as PublicKey does."""
+    r = new_tss_batch([commitments], num_shares, engine)[0]
+    if isinstance(r, Exception):
+        raise r
+    return r
+
+
+def feldman_verify_batch(items, engine=None):
+    """Feldman share verification (kryptology FeldmanVerifier.Verify, the check
+    a DKG participant runs on every share it receives): items is a list of
+    (commitments, SecretKeyShare); item k is True when [value] g1 equals the
+    verifier's polynomial evaluated at the share's identifier.  ONE
+    eval_commitments launch for the public side and ONE launch of the hardened
+    signer (tbg_sk_to_pk_ct: the share is a real secret) for [value] g1; the two
+    48-byte encodings are compared here.  A zero or out-of-range share value is
+    False; a verifier that does not decode (or has no group key) is a TblsError
+    with new_tss's string."""
+    items = [(_verifier_bytes(v), s) for v, s in items]
+    if not items:
+        return []
+    e = _engine(engine)
+    res = _eval_verifiers([v for v, _ in items], [[s.identifier] for _, s in items], e)
+    # (a value that does not fit 32 bytes is sent as 0: refused like a zero share)
+    sk = b"".join(int(s.value).to_bytes(32, "big") if 0 <= int(s.value) < 1 << 256 else bytes(32) for _, s in items)
+    pks, kst = e.sk_to_pk_ct(sk)
+    out = []
+    for (rhs, st, cst), pk, ks in zip(res, pks, kst.tolist()):
+        if st[0] not in (eng.FV_OK, eng.FV_IDENTITY):
+            out.append(_fv_error(st[0], cst))
+        else:
+            out.append(ks == eng.KS_OK and bytes(pk) == bytes(rhs[0]))
+    return out
 
 
 def generate_tss(t: int, n: int, rng, engine=None, hardened=False):

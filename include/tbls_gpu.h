@@ -477,6 +477,36 @@ int tbg_sk_to_pk_ct(tbg_ctx* ctx, const uint8_t* sk32, uint32_t n, uint8_t* pk48
 int tbg_sign_ct(tbg_ctx* ctx, const uint8_t* sk32, uint32_t n, const uint8_t* msgs, const uint32_t* msg_off,
                 uint32_t n_msgs, const uint32_t* item_msg, uint8_t* sig96, int32_t* status);
 
+/* tbls.NewTSS / getPubShare (reference tbls/tss.go:95-116, :293-325) and the
+ * right-hand side of Feldman share verification: commitment polynomials
+ * evaluated in G1.  commit48 holds the 48-byte commitments C_j = [a_j] G1 of
+ * n_polys polynomials; polynomial p owns [poly_first[p], poly_first[p + 1]),
+ * lowest coefficient first (poly_first[0] = 0, no polynomial empty).
+ * Evaluation e is polynomial eval_poly[e] at the identifier eval_id[e]:
+ *   out48[e] = C_0 + [id] C_1 + [id^2] C_2 + ... + [id^(t-1)] C_(t-1),
+ * compressed.  All of it is public data (variable time).  Every commitment is
+ * decoded as a public key is (flags, field, curve, subgroup); commit_status
+ * (optional) receives 0, 1 for the identity encoding -- which is a valid
+ * coefficient commitment -- or TBG_PS_ERR_FLAGS / _FIELD / _CURVE / _SUBGROUP.
+ * eval_status[e], in this precedence (a failed polynomial does not disturb
+ * the others):
+ *   TBG_FV_ID            eval_id[e] == 0                        out48[e] zero
+ *   TBG_FV_COMMIT        a commitment of the polynomial failed  out48[e] zero
+ *   TBG_FV_KEY_IDENTITY  C_0 is the identity (no group key)     out48[e] zero
+ *   TBG_FV_IDENTITY      the evaluation is the identity         out48[e] = c0 00 .. 00
+ *   TBG_FV_OK                                                   the compressed point
+ * TBG_E_INVALID_ARG: a required pointer is NULL, poly_first[0] != 0,
+ * poly_first decreases, a polynomial is empty, eval_poly[e] >= n_polys.
+ * n_evals == 0 (with any n_polys, 0 included): TBG_OK, nothing is launched. */
+#define TBG_FV_OK 0
+#define TBG_FV_ID (-50)
+#define TBG_FV_COMMIT (-51)
+#define TBG_FV_KEY_IDENTITY (-52)
+#define TBG_FV_IDENTITY (-53)
+int tbg_eval_commitments(tbg_ctx* ctx, const uint8_t* commit48, const uint32_t* poly_first, uint32_t n_polys,
+                         const uint32_t* eval_poly, const uint32_t* eval_id, uint32_t n_evals, uint8_t* out48,
+                         int32_t* eval_status, int32_t* commit_status);
+
 /* Last kernel timings of the context (milliseconds, HIP events on the
  * engine's streams): [decode, hash, combine (RLC sums + group lines),
  * H lines, verify (all check levels), lagrange, aggregate, total]; ms8 has
