@@ -315,6 +315,13 @@ SIGNATURES = {
     "tbg_eval_commitments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p]),
+    # shares on a fixed schedule.  split: coef32, poly_first, n_polys, n_shares, share32, commit48,
+    # pubshare48 (optional), status; combine: share32, share_id, set_first, n_sets, secret32, status
+    "tbg_split_secret_ct": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
+    "tbg_combine_shares_ct": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     # include/tbls_ssz.h (host code)
     "tbg_ssz_size": (ctypes.c_uint32, [ctypes.c_uint32]),
     "tbg_ssz_roots": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_void_p,

@@ -1513,7 +1513,8 @@ namespace {
 
 // TBG_KS_* of a 32-byte big-endian key: zero, or a word-wise compare against
 // r -- every word is read and subtracted whatever the earlier ones were.
-int32_t keyed_status(const uint8_t* b) {
+// (zero_code / range_code: the caller's codes for the two refusals)
+int32_t range_status(const uint8_t* b, int32_t zero_code, int32_t range_code) {
   static const uint32_t R_W[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u,
                                   0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};  // r, little-endian words
   uint32_t nz = 0;
@@ -1526,50 +1527,84 @@ int32_t keyed_status(const uint8_t* b) {
   }
   const int32_t ge = (int32_t)borrow - 1;                      // all ones: sk >= r (no final borrow)
   const int32_t zero = (int32_t)((nz | (0u - nz)) >> 31) - 1;  // all ones: sk == 0
-  return (TBG_KS_ZERO & zero) | (TBG_KS_RANGE & ge & ~zero);
+  return (zero_code & zero) | (range_code & ge & ~zero);
 }
+int32_t keyed_status(const uint8_t* b) { return range_status(b, TBG_KS_ZERO, TBG_KS_RANGE); }
+
+// all ones iff v != 0
+inline int32_t nz_mask(int32_t v) { return 0 - (int32_t)(((uint32_t)v | (0u - (uint32_t)v)) >> 31); }
 
 void keyed_wipe(void* p, size_t n) {
   volatile uint8_t* v = (volatile uint8_t*)p;
   for (size_t i = 0; i < n; ++i) v[i] = 0;
 }
 
-// The scope of a hardened call: CallScope and everything that held key bytes
-// -- the device copy of the keys (the workspace's `sk` section) and the pinned
-// staging they were uploaded from.  Whatever way the call ends, the device
-// bytes are zeroed ON THE STREAM (behind the kernels that read them), the
-// stream is drained, the staging is zeroed, and only then is either released
-// (the workspace by ~CallScope, which runs after this destructor).
+// 32 bytes into the staging: k itself (keep = 0xff) or the scalar 1 (keep = 0), by masks
+inline void stage_scalar(uint8_t* dst, const uint8_t* k, uint8_t keep) {
+  for (int j = 0; j < 32; ++j) dst[j] = (uint8_t)((k[j] & keep) | ((j == 31 ? 1 : 0) & ~keep));
+}
+
+// The scope of a call that holds secrets: CallScope and everything that held
+// secret bytes -- the device sections the call's workspace names in secrets()
+// and every pinned staging buffer the call took from stage().  Whatever way
+// the call ends, the device bytes are zeroed ON THE STREAM (behind the kernels
+// and copies that use them), the stream is drained, the staging is zeroed, and
+// only then is either released (the workspace by ~CallScope, which runs after
+// this destructor).
 struct KeyedScope : CallScope {
-  uint8_t* d_sk = nullptr;  // [sk_bytes] inside the workspace
-  uint8_t* h_sk = nullptr;  // [sk_bytes] pinned (hipHostMalloc)
-  size_t sk_bytes = 0;
+  struct Region {
+    uint8_t* p;
+    size_t bytes;
+  };
+  static constexpr uint32_t kMaxRegions = 8;
+  Region dev[kMaxRegions] = {};   // inside the workspace
+  Region pin[kMaxRegions] = {};   // pinned (hipHostMalloc)
+  uint32_t n_dev = 0, n_pin = 0;
   using CallScope::CallScope;
   ~KeyedScope() {
-    if (d_sk) (void)hipMemsetAsync(d_sk, 0, sk_bytes, st);
+    for (uint32_t i = 0; i < n_dev; ++i)
+      if (dev[i].bytes) (void)hipMemsetAsync(dev[i].p, 0, dev[i].bytes, st);
     (void)hipStreamSynchronize(st);
-    if (h_sk) {
-      keyed_wipe(h_sk, sk_bytes);
-      (void)hipHostFree(h_sk);
+    for (uint32_t i = 0; i < n_pin; ++i) {
+      keyed_wipe(pin[i].p, pin[i].bytes);
+      (void)hipHostFree(pin[i].p);
     }
   }
-  // w's workspace and the staging; the keys go into the staging with every
-  // rejected one replaced by 1 (masks, no branch on a key byte), their codes into kst.
+  // w's workspace; the sections w.secrets() names become the scope's to wipe
   template <class W>
-  int open(W& w, const uint8_t* sk32, uint32_t n, std::vector<int32_t>& kst) {
-    sk_bytes = 32ull * n;
+  int open(W& w) {
     const int rc = CallScope::open(w);
     if (rc != TBG_OK) return rc;
-    if (hipHostMalloc((void**)&h_sk, sk_bytes, hipHostMallocDefault) != hipSuccess) { h_sk = nullptr; return TBG_E_OOM; }
+    auto take = [&](const char*, uint8_t*& p, size_t count, size_t = 0) {
+      plan_check(n_dev < kMaxRegions, "more secret sections than KeyedScope::kMaxRegions");
+      dev[n_dev++] = Region{p, count};
+    };
+    w.secrets(take);
+    return TBG_OK;
+  }
+  // a pinned staging buffer of the scope (zero-filled); null when the host cannot pin it
+  uint8_t* stage(size_t bytes) {
+    uint8_t* h = nullptr;
+    if (n_pin >= kMaxRegions || hipHostMalloc((void**)&h, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) return nullptr;
+    pin[n_pin++] = Region{h, bytes};
+    memset(h, 0, bytes);
+    return h;
+  }
+  // the hardened signer's: w's workspace and the keys' staging; the keys go into the staging
+  // with every rejected one replaced by 1 (masks, no branch on a key byte), their codes into kst.
+  template <class W>
+  int open(W& w, const uint8_t* sk32, uint32_t n, std::vector<int32_t>& kst) {
+    const int rc = open(w);
+    if (rc != TBG_OK) return rc;
+    uint8_t* h_sk = stage(32ull * n);
+    if (!h_sk) return TBG_E_OOM;
     kst.resize(n);
     for (uint32_t i = 0; i < n; ++i) {
       const uint8_t* k = sk32 + 32ull * i;
       kst[i] = keyed_status(k);
-      const uint8_t keep = (uint8_t)(((uint32_t)kst[i] | (0u - (uint32_t)kst[i])) >> 31) - 1;  // 0xff: accepted
-      for (int j = 0; j < 32; ++j) h_sk[32ull * i + j] = (uint8_t)((k[j] & keep) | ((j == 31 ? 1 : 0) & ~keep));
+      stage_scalar(h_sk + 32ull * i, k, (uint8_t)~nz_mask(kst[i]));  // 0xff: accepted
     }
-    d_sk = w.sk;
-    return hipMemcpyAsync(d_sk, h_sk, sk_bytes, hipMemcpyHostToDevice, st) == hipSuccess ? TBG_OK : TBG_E_DEVICE;
+    return hipMemcpyAsync(w.sk, h_sk, 32ull * n, hipMemcpyHostToDevice, st) == hipSuccess ? TBG_OK : TBG_E_DEVICE;
   }
 };
 
@@ -1642,6 +1677,154 @@ int tbg_sign_ct(tbg_ctx* c, const uint8_t* sk32, uint32_t n, const uint8_t* msgs
   rc = ks.drain(rc);
   if (rc == TBG_OK) keyed_mask(kst, sig96, 96, status);
   return rc;
+}
+
+// ---- shares on a fixed schedule (k_shares.hip, bls_frct.h) -----------------
+// tbls/tss.go:256-290 (SplitSecret), :120-139 (GenerateTSS), :220-253
+// (CombineShares).  The secret arithmetic in Fr runs on the device; the
+// commitments and pubshares are the hardened signer's ladder over the
+// coefficient section and the ladder-scalar section.  Secret outputs come back
+// through the scope's pinned staging, never straight into caller memory.
+int tbg_split_secret_ct(tbg_ctx* c, const uint8_t* coef32, const uint32_t* poly_first, uint32_t n_polys,
+                        uint32_t n_shares, uint8_t* share32, uint8_t* commit48, uint8_t* pubshare48, int32_t* status) {
+  if (!c || n_shares < 1 || n_shares > 255) return TBG_E_INVALID_ARG;
+  if (n_polys == 0) return TBG_OK;
+  if (!coef32 || !poly_first || !share32 || !commit48 || !status || poly_first[0] != 0) return TBG_E_INVALID_ARG;
+  if ((uint64_t)n_polys * n_shares > 0x7fffffffull) return TBG_E_INVALID_ARG;
+  for (uint32_t p = 0; p < n_polys; ++p) {
+    if (poly_first[p + 1] < poly_first[p]) return TBG_E_INVALID_ARG;
+    const uint32_t t = poly_first[p + 1] - poly_first[p];
+    if (t < 2 || t > n_shares) return TBG_E_INVALID_ARG;  // (NewFeldman: 2 <= t <= n)
+  }
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  const uint32_t nc = poly_first[n_polys], ne = n_polys * n_shares;
+  SplitSecretCtWork w;
+  w.n_coefs = nc;
+  w.n_polys = n_polys;
+  w.n_evals = ne;
+  w.tab_words = ct_tab_words_g1();
+  std::vector<int32_t> pst(n_polys);
+  std::vector<uint32_t> zf(ne);
+  KeyedScope ks(c->stream);
+  int rc = ks.open(w);
+  if (rc != TBG_OK) return rc;
+  uint8_t* h_coef = ks.stage(32ull * nc);
+  uint8_t* h_share = ks.stage(32ull * ne);
+  if (!h_coef || !h_share) return TBG_E_OOM;
+  // every coefficient's code is formed; the first one by index is the polynomial's, and a
+  // refused polynomial goes up as all ones (masks, no branch on a coefficient byte)
+  for (uint32_t p = 0; p < n_polys; ++p) {
+    int32_t code = 0;
+    for (uint32_t j = poly_first[p]; j < poly_first[p + 1]; ++j)
+      code |= range_status(coef32 + 32ull * j, TBG_SH_COEF_ZERO, TBG_SH_COEF_RANGE) & ~nz_mask(code);
+    pst[p] = code;
+    for (uint32_t j = poly_first[p]; j < poly_first[p + 1]; ++j)
+      stage_scalar(h_coef + 32ull * j, coef32 + 32ull * j, (uint8_t)~nz_mask(code));
+  }
+  hipStream_t st = c->stream;
+  if (hipMemcpyAsync(w.coef, h_coef, 32ull * nc, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(w.poly_first, poly_first, 4ull * (n_polys + 1), hipMemcpyHostToDevice, st) != hipSuccess)
+    rc = TBG_E_DEVICE;
+  if (rc == TBG_OK) {
+    launch_split_ct(w.coef, nc, w.poly_first, n_polys, n_shares, w.share, w.ladder, w.share_zero, st);
+    launch_ct_table_g1(w.tab, st);
+    launch_sk_to_pk_ct(w.coef, nc, w.tab, w.commit, w.ks_status, st);
+    if (pubshare48) launch_sk_to_pk_ct(w.ladder, ne, w.tab, w.pubshare, w.ks_status, st);
+    if (hipGetLastError() != hipSuccess) rc = TBG_E_DEVICE;
+  }
+  if (rc == TBG_OK &&
+      (hipMemcpyAsync(h_share, w.share, 32ull * ne, hipMemcpyDeviceToHost, st) != hipSuccess ||
+       hipMemcpyAsync(zf.data(), w.share_zero, 4ull * ne, hipMemcpyDeviceToHost, st) != hipSuccess ||
+       hipMemcpyAsync(commit48, w.commit, 48ull * nc, hipMemcpyDeviceToHost, st) != hipSuccess ||
+       (pubshare48 && hipMemcpyAsync(pubshare48, w.pubshare, 48ull * ne, hipMemcpyDeviceToHost, st) != hipSuccess)))
+    rc = TBG_E_DEVICE;
+  rc = ks.drain(rc);
+  if (rc != TBG_OK) return rc;
+  for (uint32_t p = 0; p < n_polys; ++p) {
+    const size_t e0 = (size_t)p * n_shares, c0 = poly_first[p], t = poly_first[p + 1] - poly_first[p];
+    uint32_t any_zero = 0;
+    for (uint32_t i = 0; i < n_shares; ++i) any_zero |= zf[e0 + i];
+    const int32_t code = pst[p] != TBG_SH_OK ? pst[p] : any_zero ? TBG_SH_SHARE_ZERO : TBG_SH_OK;  // (the code is public)
+    status[p] = code;
+    if (code == TBG_SH_OK) {
+      memcpy(share32 + 32 * e0, h_share + 32 * e0, 32ull * n_shares);
+    } else {
+      memset(share32 + 32 * e0, 0, 32ull * n_shares);
+      memset(commit48 + 48 * c0, 0, 48 * t);
+      if (pubshare48) memset(pubshare48 + 48 * e0, 0, 48ull * n_shares);
+    }
+  }
+  return TBG_OK;
+}
+
+int tbg_combine_shares_ct(tbg_ctx* c, const uint8_t* share32, const uint8_t* share_id, const uint32_t* set_first,
+                          uint32_t n_sets, uint8_t* secret32, int32_t* status) {
+  if (!c) return TBG_E_INVALID_ARG;
+  if (n_sets == 0) return TBG_OK;
+  if (!set_first || !secret32 || !status || set_first[0] != 0) return TBG_E_INVALID_ARG;
+  for (uint32_t k = 0; k < n_sets; ++k)
+    if (set_first[k + 1] < set_first[k]) return TBG_E_INVALID_ARG;
+  const uint32_t nv = set_first[n_sets];
+  if (nv && (!share32 || !share_id)) return TBG_E_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  CombineSharesCtWork w;
+  w.n_values = nv;
+  w.n_sets = n_sets;
+  std::vector<int32_t> sst(n_sets);
+  std::vector<uint32_t> ok(n_sets), zf(n_sets);
+  KeyedScope ks(c->stream);
+  int rc = ks.open(w);
+  if (rc != TBG_OK) return rc;
+  uint8_t* h_value = ks.stage(32ull * nv);
+  uint8_t* h_secret = ks.stage(32ull * n_sets);
+  if (!h_value || !h_secret) return TBG_E_OOM;
+  for (uint32_t k = 0; k < n_sets; ++k) {
+    const uint32_t first = set_first[k], last = set_first[k + 1];
+    // the public reasons (sizes and identifiers are public), in their precedence
+    int32_t code = TBG_SH_OK;
+    bool seen[256] = {}, id_zero = false, dup = false;
+    for (uint32_t i = first; i < last; ++i) {
+      id_zero |= share_id[i] == 0;
+      dup |= seen[share_id[i]];
+      seen[share_id[i]] = true;
+    }
+    if (last - first < 2) code = TBG_SH_TOO_FEW;
+    else if (id_zero) code = TBG_SH_ID;
+    else if (dup) code = TBG_SH_DUPLICATE_ID;
+    // then the values: every one's code is formed, the first by index counts (masks)
+    int32_t vcode = 0;
+    for (uint32_t i = first; i < last; ++i)
+      vcode |= range_status(share32 + 32ull * i, TBG_SH_VALUE_ZERO, TBG_SH_VALUE_RANGE) & ~nz_mask(vcode);
+    code |= vcode & ~nz_mask(code);
+    sst[k] = code;
+    ok[k] = (uint32_t)~nz_mask(code) & 1u;
+    for (uint32_t i = first; i < last; ++i)
+      stage_scalar(h_value + 32ull * i, share32 + 32ull * i, (uint8_t)~nz_mask(code));
+  }
+  hipStream_t st = c->stream;
+  if ((nv && (hipMemcpyAsync(w.value, h_value, 32ull * nv, hipMemcpyHostToDevice, st) != hipSuccess ||
+              hipMemcpyAsync(w.share_id, share_id, nv, hipMemcpyHostToDevice, st) != hipSuccess)) ||
+      hipMemcpyAsync(w.set_first, set_first, 4ull * (n_sets + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(w.set_ok, ok.data(), 4ull * n_sets, hipMemcpyHostToDevice, st) != hipSuccess)
+    rc = TBG_E_DEVICE;
+  if (rc == TBG_OK) {
+    launch_combine_ct(w.value, w.share_id, nv, w.set_first, w.set_ok, n_sets, w.secret, w.secret_zero, st);
+    if (hipGetLastError() != hipSuccess) rc = TBG_E_DEVICE;
+  }
+  if (rc == TBG_OK && (hipMemcpyAsync(h_secret, w.secret, 32ull * n_sets, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                       hipMemcpyAsync(zf.data(), w.secret_zero, 4ull * n_sets, hipMemcpyDeviceToHost, st) != hipSuccess))
+    rc = TBG_E_DEVICE;
+  rc = ks.drain(rc);
+  if (rc != TBG_OK) return rc;
+  for (uint32_t k = 0; k < n_sets; ++k) {
+    const int32_t code = sst[k] != TBG_SH_OK ? sst[k] : zf[k] ? TBG_SH_SECRET_ZERO : TBG_SH_OK;  // (public)
+    status[k] = code;
+    if (code == TBG_SH_OK) memcpy(secret32 + 32ull * k, h_secret + 32ull * k, 32);
+    else memset(secret32 + 32ull * k, 0, 32);
+  }
+  return TBG_OK;
 }
 
 // ---- plain sums and FastAggregateVerify (k_sum.hip) -----------------------

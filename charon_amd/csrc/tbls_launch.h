@@ -603,5 +603,13 @@ void launch_sign_ct(const uint8_t* sk32, const uint32_t* item_msg, uint32_t n, u
 void launch_fv_eval(const G1A* tab, const int32_t* tab_status, uint32_t n_commits, const uint32_t* poly_first,
                     uint32_t n_polys, const uint32_t* eval_poly, const uint32_t* eval_id, uint32_t n_evals, uint8_t* out48,
                     int32_t* status, hipStream_t st);
+// shares on a fixed schedule (k_shares.hip, bls_frct.h).  Split: one lane per (polynomial, identifier
+// 1..n_shares) -- the share, the share with a zero replaced by 1 (the ladder's scalar) and a zero flag per
+// lane.  Combine: one lane per set -- the interpolation at 0 over all its shares and a zero flag; a set with
+// set_ok == 0 is not computed.
+void launch_split_ct(const uint8_t* coef32, uint32_t n_coefs, const uint32_t* poly_first, uint32_t n_polys,
+                     uint32_t n_shares, uint8_t* share32, uint8_t* ladder32, uint32_t* zero, hipStream_t st);
+void launch_combine_ct(const uint8_t* value32, const uint8_t* share_id, uint32_t n_values, const uint32_t* set_first,
+                       const uint32_t* set_ok, uint32_t n_sets, uint8_t* secret32, uint32_t* zero, hipStream_t st);
 
 }  // namespace tbg

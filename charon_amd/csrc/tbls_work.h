@@ -1,8 +1,9 @@
 // The workspace of every call that runs to completion inside itself --
 // tbg_sk_to_pk, tbg_sign, their hardened forms, the plain sums,
-// tbg_fast_aggregate_verify and tbg_eval_commitments: one struct per call whose sections() names every
-// section of the call's single device allocation once, with its element type
-// and count, in arena order.  The size comes from one walk of it with a null
+// tbg_fast_aggregate_verify, tbg_eval_commitments and the two share calls: one struct per call whose
+// sections() names every section of the call's single device allocation once, with its element type
+// and count, in arena order.  A call that holds secrets names the sections that hold them once more,
+// in secrets(): the call's scope zeroes exactly that list before the allocation is released.  The size comes from one walk of it with a null
 // base and the pointers from a second walk over the allocation (work_size,
 // work_bind), the way for_each_section serves layout and bind for a launch.
 // No HIP runtime call in here: tests/plan walks the descriptions on the CPU.
@@ -76,6 +77,10 @@ struct SkToPkCtWork {  // tbg_sk_to_pk_ct
     v("pk", pk, 48 * n);
     v("status", status, n);
   }
+  template <class V>
+  void secrets(V& v) {
+    v("sk", sk, 32 * n);
+  }
 };
 
 struct SignWork {  // tbg_sign
@@ -108,6 +113,10 @@ struct SignCtWork : SignWork {  // tbg_sign_ct: tbg_sign's, then the tables and 
     SignWork::sections(v);
     v("tab", tab, tab_words);
     v("status", status, n);
+  }
+  template <class V>
+  void secrets(V& v) {
+    v("sk", sk, 32 * n);
   }
 };
 
@@ -224,6 +233,60 @@ struct EvalCommitWork {
     v("commit_status", commit_status, n_commits);
     v("out48", out48, 48 * n_evals);
     v("eval_status", eval_status, n_evals);
+  }
+};
+
+// tbg_split_secret_ct: n_coefs coefficients in n_polys polynomials, n_evals = n_polys * n_shares
+// shares.  ks_status: what the two ladder launches write (max(n_coefs, n_evals) words).
+struct SplitSecretCtWork {
+  size_t n_coefs = 0, n_polys = 0, n_evals = 0, tab_words = 0;  // tab_words: ct_tab_words_g1()
+  uint8_t* coef = nullptr;
+  uint32_t* poly_first = nullptr;
+  uint32_t* tab = nullptr;
+  uint8_t *share = nullptr, *ladder = nullptr;
+  uint32_t* share_zero = nullptr;
+  uint8_t *commit = nullptr, *pubshare = nullptr;
+  int32_t* ks_status = nullptr;
+  template <class V>
+  void sections(V& v) {
+    v("coef", coef, 32 * n_coefs);
+    v("poly_first", poly_first, n_polys + 1);
+    v("tab", tab, tab_words);
+    v("share", share, 32 * n_evals);
+    v("ladder", ladder, 32 * n_evals);
+    v("share_zero", share_zero, n_evals);
+    v("commit", commit, 48 * n_coefs);
+    v("pubshare", pubshare, 48 * n_evals);
+    v("ks_status", ks_status, n_coefs > n_evals ? n_coefs : n_evals);
+  }
+  template <class V>
+  void secrets(V& v) {
+    v("coef", coef, 32 * n_coefs);
+    v("share", share, 32 * n_evals);
+    v("ladder", ladder, 32 * n_evals);
+  }
+};
+
+// tbg_combine_shares_ct: n_values share values in n_sets sets.
+struct CombineSharesCtWork {
+  size_t n_values = 0, n_sets = 0;
+  uint8_t *value = nullptr, *share_id = nullptr;
+  uint32_t *set_first = nullptr, *set_ok = nullptr;
+  uint8_t* secret = nullptr;
+  uint32_t* secret_zero = nullptr;
+  template <class V>
+  void sections(V& v) {
+    v("value", value, 32 * n_values, 16);
+    v("share_id", share_id, n_values, 16);
+    v("set_first", set_first, n_sets + 1);
+    v("set_ok", set_ok, n_sets);
+    v("secret", secret, 32 * n_sets);
+    v("secret_zero", secret_zero, n_sets);
+  }
+  template <class V>
+  void secrets(V& v) {
+    v("value", value, 32 * n_values);
+    v("secret", secret, 32 * n_sets);
   }
 };
 

@@ -263,7 +263,8 @@ def agg_sign_lock_hash(share_lists, lock_hash: bytes, engine=None) -> bytes:
     return bytes(agg[0])
 
 
-def create_cluster_tss(secrets, t: int, n: int, rng, engine=None, hardened=False, from_commitments=False):
+def create_cluster_tss(secrets, t: int, n: int, rng, engine=None, hardened=False, from_commitments=False,
+                       device_split=False):
     """getTSSShares of `charon create cluster` (cmd/createcluster.go:250-270):
     every validator secret split t-of-n and its TSS.  One split on the host
     (integers), ONE sk_to_pk launch for every commitment and every pubshare
@@ -275,7 +276,7 @@ def create_cluster_tss(secrets, t: int, n: int, rng, engine=None, hardened=False
     production keys (tbls.split_secret).  hardened=True forms every commitment
     and pubshare on the fixed schedule (tbg_sk_to_pk_ct; a zero or out-of-range
     scalar raises); the split itself stays on host integers and keeps the
-    warning -- the product's caller is Go, which splits in kryptology.
+    warning -- device_split (below) moves it to the device as well.
 
     from_commitments=True derives the pubshares the way NewTSS does: the
     scalar-multiplication launch forms the V*t commitments only (hardened or
@@ -283,8 +284,22 @@ def create_cluster_tss(secrets, t: int, n: int, rng, engine=None, hardened=False
     1..n for all V*n pubshares, and no share value reaches the device.  Same
     return value, errors and residency.  Off by default: at large thresholds
     (170-of-255) Horner's rule over the commitments needs more group
-    operations than one 256-bit ladder per share."""
+    operations than one 256-bit ladder per share.
+
+    device_split=True is the ceremony for keys that matter: ONE
+    Engine.split_secret_ct call (tbg_split_secret_ct) evaluates every
+    polynomial on the device in masks and forms every commitment and pubshare
+    with the fixed-schedule ladder from the device copies -- no share travels
+    back to the host between the split and its ladder -- then the same
+    key_from_bytes_batch.  The coefficients are drawn from ``rng`` in the same
+    order, so the return value equals the hardened=True path's.  A secret is
+    sent as given: zero or >= r raises instead of being reduced mod r.  It
+    implies hardened and does not combine with from_commitments."""
     e = tbls._engine(engine)
+    if device_split:
+        if from_commitments:
+            raise tbls.TblsError("create cluster: device_split forms the pubshares itself (no from_commitments)")
+        return _create_cluster_tss_device(list(secrets), t, n, rng, e)
     splits, polys = [], []
     for s in secrets:
         shares, poly = tbls._split_host(s, t, n, rng)
@@ -320,6 +335,31 @@ def create_cluster_tss(secrets, t: int, n: int, rng, engine=None, hardened=False
         c = commits[d * t:(d + 1) * t]
         dvs.append(tbls.TSS(pub, n, t, tbls.PublicKey(c[0]), tuple(c)))
     return dvs, splits
+
+
+def _create_cluster_tss_device(secrets, t, n, rng, e):
+    """create_cluster_tss(device_split=True): the split, the commitments and the pubshares of every
+    validator in one engine call."""
+    if not (2 <= t <= n <= 255):
+        raise tbls.TblsError("new Feldman VSS: need 2 <= t <= n <= 255")
+    if not secrets:
+        return [], []
+    polys = [[int(s)] + [rng.randrange(1, tbls.R) for _ in range(t - 1)] for s in secrets]
+    res = tbls._split_device(polys, n, e)
+    for r in res:
+        if isinstance(r, Exception):
+            raise r
+    keys = tbls.key_from_bytes_batch([pk for _, _, pks in res for pk in pks], e)
+    dvs = []
+    for d, (_, commits, _) in enumerate(res):
+        pub = {}
+        for i in range(n):
+            k = keys[d * n + i]
+            if isinstance(k, Exception):
+                raise tbls.TblsError(str(k).replace("unmarshal pubkey", "unmarshal pubshare"))
+            pub[i + 1] = k
+        dvs.append(tbls.TSS(pub, n, t, tbls.PublicKey(commits[0]), tuple(commits)))
+    return dvs, [shares for shares, _, _ in res]
 
 
 def _lock_bytes(v) -> bytes:

@@ -28,6 +28,9 @@ SS_ERROR, SS_INVALID, SS_VALID = 30, 31, 32
 KS_OK, KS_ZERO, KS_RANGE, KS_MSG = 0, -40, -41, -42
 # per-evaluation status of eval_commitments (TBG_FV_*), in their precedence
 FV_OK, FV_ID, FV_COMMIT, FV_KEY_IDENTITY, FV_IDENTITY = 0, -50, -51, -52, -53
+# per-polynomial / per-set status of split_secret_ct / combine_shares_ct (TBG_SH_*)
+SH_OK, SH_COEF_ZERO, SH_COEF_RANGE, SH_SHARE_ZERO = 0, -60, -61, -62
+SH_TOO_FEW, SH_ID, SH_DUPLICATE_ID, SH_VALUE_ZERO, SH_VALUE_RANGE, SH_SECRET_ZERO = -63, -64, -65, -66, -67, -68
 OP_VERIFY, OP_AGGREGATE, OP_VERIFY_AGGREGATE = 1, 2, 3
 # aggregate every duty, then CoreVerify the aggregate under the duty's group key, in one
 # launch: pubkey_ids holds one resident id per DUTY
@@ -471,6 +474,45 @@ class Engine:
         self._check(self._lib.tbg_eval_commitments(self._h, _ptr(a), _ptr(pf), n_polys, _ptr(ep), _ptr(ei), n, _ptr(out),
                                                    _ptr(st), _ptr(cst)), "tbg_eval_commitments")
         return out, st, cst
+
+    # ---- shares on a fixed schedule (tbls.SplitSecret / GenerateTSS / CombineShares) ----
+    def split_secret_ct(self, coef32, poly_first, n_shares, pubshares=True):
+        """tbg_split_secret_ct: polynomial p owns the 32-byte big-endian coefficients
+        [poly_first[p], poly_first[p + 1]), lowest first (coefficient 0: the secret) ->
+        (share32 [n_polys * n_shares, 32], commit48 [n_coefs, 48], pubshare48
+        [n_polys * n_shares, 48] or None without pubshares, status [n_polys] of SH_*).
+        A failed polynomial has all its outputs zero."""
+        pf = _u32(poly_first)
+        a = _u8(coef32, 32) if len(coef32) else np.zeros((0, 32), np.uint8)
+        n_polys = max(len(pf) - 1, 0)
+        if n_polys and int(pf[-1]) != a.shape[0]:
+            raise ValueError("poly_first must end at the number of coefficients")
+        n = int(n_shares)
+        ne = n_polys * n if 1 <= n <= 255 else 0
+        shares = np.zeros((ne, 32), dtype=np.uint8)
+        commits = np.zeros((a.shape[0], 48), dtype=np.uint8)
+        pub = np.zeros((ne, 48), dtype=np.uint8) if pubshares else None
+        st = np.zeros(n_polys, dtype=np.int32)
+        self._check(self._lib.tbg_split_secret_ct(self._h, _ptr(a), _ptr(pf), n_polys, n & 0xFFFFFFFF, _ptr(shares),
+                                                  _ptr(commits), _ptr(pub), _ptr(st)), "tbg_split_secret_ct")
+        return shares, commits, pub, st
+
+    def combine_shares_ct(self, share32, ids, set_first):
+        """tbg_combine_shares_ct: set k owns the shares [set_first[k], set_first[k + 1]) --
+        ids[i] the identifier byte, share32[i] the 32-byte big-endian value -> (secret32
+        [n_sets, 32], status [n_sets] of SH_*): the interpolation at 0 over all of a set's
+        shares.  A failed set has a zero secret."""
+        sf = _u32(set_first)
+        a = _u8(share32, 32) if len(share32) else np.zeros((0, 32), np.uint8)
+        idb = _u8(bytes(bytearray(int(i) for i in ids))) if len(ids) else np.zeros(0, np.uint8)
+        n_sets = max(len(sf) - 1, 0)
+        if len(idb) != a.shape[0] or (n_sets and int(sf[-1]) != a.shape[0]):
+            raise ValueError("ids, share32 and set_first must describe the same shares")
+        out = np.zeros((n_sets, 32), dtype=np.uint8)
+        st = np.zeros(n_sets, dtype=np.int32)
+        self._check(self._lib.tbg_combine_shares_ct(self._h, _ptr(a), _ptr(idb), _ptr(sf), n_sets, _ptr(out), _ptr(st)),
+                    "tbg_combine_shares_ct")
+        return out, st
 
 
 class MultiEngine:

@@ -435,8 +435,9 @@ def split_secret(secret: int, t: int, n: int, rng, engine=None, hardened=False):
     engine's sk_to_pk is the test-only double-and-add of tbg_sk_to_pk -- not
     for production keys.  hardened=True forms the commitments on the fixed
     schedule (tbg_sk_to_pk_ct); the polynomial is still split here on host
-    integers and keeps this warning -- the product's caller is Go, which
-    splits in kryptology."""
+    integers and keeps this warning.  A key that matters is split by
+    split_secret_batch (tbg_split_secret_ct), which evaluates the polynomial
+    on the device in masks and gives the same shares for the same rng."""
     shares, poly = _split_host(secret, t, n, rng)
     return shares, _sk_to_pk(poly, engine, hardened, "marshalling Secret Key")
 
@@ -616,7 +617,9 @@ def generate_tss(t: int, n: int, rng, engine=None, hardened=False):
     """tbls.GenerateTSS (tss.go:120-139): a random secret split t-of-n and its
     TSS.  Returns (TSS, shares, secret); the secret is returned for the parity
     tests (the reference discards it).  Test clusters only: see split_secret
-    (hardened=True: every scalar multiplication on the fixed schedule)."""
+    (hardened=True: every scalar multiplication on the fixed schedule, the
+    split itself still on host integers).  generate_tss_batch runs the split
+    on the device too and returns the same values for the same rng."""
     secret = rng.randrange(1, R)
     try:
         shares, commits = split_secret(secret, t, n, rng, engine, hardened=hardened)
@@ -628,7 +631,9 @@ def generate_tss(t: int, n: int, rng, engine=None, hardened=False):
 def combine_shares(shares, t: int, n: int) -> int:
     """tbls.CombineShares (tss.go:220-253): the secret from at least t shares,
     Lagrange interpolation at 0 mod r over ALL shares given.  Host integers,
-    not side-channel safe: not for production keys."""
+    not side-channel safe: not for production keys -- those go through
+    combine_shares_batch (tbg_combine_shares_ct), which interpolates on the
+    device in masks."""
     shares = list(shares)
     if not (2 <= t <= n <= 255):
         raise TblsError("new Feldman VSS: need 2 <= t <= n <= 255")
@@ -740,3 +745,131 @@ def secret_to_public_key_batch(secrets, engine=None):
     pks, st = _engine(engine).sk_to_pk_ct(b"".join(_sk32_exact(s) for s in secrets))
     return [PublicKey(bytes(pk)) if s == eng.KS_OK else TblsError("secret to pubkey: " + _KS_ERRORS.get(s, f"status {s}"))
             for pk, s in zip(pks, st.tolist())]
+
+
+# ------------------------------------------------------------ shares on a fixed schedule
+# tbg_split_secret_ct / tbg_combine_shares_ct (include/tbls_gpu.h): the Fr
+# arithmetic of SplitSecret, GenerateTSS and CombineShares on the device, in
+# masks -- what split_secret and combine_shares do on host integers.  Same
+# limits as the hardened signer: the Python integers a caller holds (and the
+# coefficients drawn here from its rng) are the caller's to guard.
+_SH_SPLIT_ERRORS = {
+    eng.SH_COEF_RANGE: "convert to scaler: a coefficient is not below the group order",
+    eng.SH_COEF_ZERO: "split Secret Key: invalid secret (a zero coefficient)",
+    eng.SH_SHARE_ZERO: "unmarshalling shamir share: secret key cannot be zero",
+}
+_SH_COMBINE_ERRORS = {
+    eng.SH_TOO_FEW: "combine shares: fewer than two shares",
+    eng.SH_ID: "combine shares: invalid share identifier",
+    eng.SH_DUPLICATE_ID: "combine shares: duplicate share identifier",
+    eng.SH_VALUE_ZERO: "combine shares: a share value is zero",
+    eng.SH_VALUE_RANGE: "combine shares: a share value is not below the group order",
+    eng.SH_SECRET_ZERO: "unmarshal secret: secret key cannot be zero",
+}
+
+
+def _split_device(polys, n: int, e, pubshares=True):
+    """ONE Engine.split_secret_ct call over integer polynomials (lowest
+    coefficient first, sent WITHOUT reduction: the engine's range check
+    decides).  Per polynomial: (shares, commitments, pubshares or None), or
+    the TblsError of its SH_* code."""
+    first = np.concatenate([[0], np.cumsum([len(p) for p in polys])]).astype(np.uint32)
+    sh, cm, pub, st = e.split_secret_ct(b"".join(_sk32_exact(c) for p in polys for c in p), first, n, pubshares)
+    out = []
+    for k, s in enumerate(st.tolist()):
+        if s != eng.SH_OK:
+            out.append(TblsError(_SH_SPLIT_ERRORS.get(s, f"split secret: status {s}")))
+            continue
+        shares = [SecretKeyShare(i + 1, int.from_bytes(bytes(sh[k * n + i]), "big")) for i in range(n)]
+        commits = [bytes(c) for c in cm[first[k]:first[k + 1]]]
+        out.append((shares, commits, [bytes(pk) for pk in pub[k * n:(k + 1) * n]] if pubshares else None))
+    return out
+
+
+def split_secret_batch(items, n: int, rng, engine=None):
+    """tbls.SplitSecret for many secrets in ONE engine call on the fixed
+    schedule (tbg_split_secret_ct): items is a list of (secret, t).  The
+    coefficients are drawn with ``rng.randrange(1, R)`` in the order sequential
+    split_secret calls draw them, so the same seed gives the same shares; the
+    polynomial is evaluated on the device in masks (csrc/bls_frct.h), and the
+    commitments and pubshares are formed by the hardened ladder from the
+    device copies.  Per item returns (shares, commitments, pubshares) or a
+    TblsError: "new Feldman VSS: ..." for a bad (t, n) (nothing is drawn, as
+    in split_secret), "convert to scaler: ..." / "split Secret Key: ..." for a
+    secret (or coefficient) the engine refuses -- it is sent as given, not
+    reduced mod r, and its t - 1 draws are consumed -- and "unmarshalling
+    shamir share: ..." when some f(i) is zero."""
+    items = [(int(s), int(t)) for s, t in items]
+    res, polys, slots = [], [], []
+    for k, (secret, t) in enumerate(items):
+        if not (2 <= t <= n <= 255):
+            res.append(TblsError("new Feldman VSS: need 2 <= t <= n <= 255"))
+            continue
+        polys.append([secret] + [rng.randrange(1, R) for _ in range(t - 1)])
+        slots.append(k)
+        res.append(None)
+    if polys:
+        for k, r in zip(slots, _split_device(polys, n, _engine(engine))):
+            res[k] = r
+    return res
+
+
+def generate_tss_batch(count: int, t: int, n: int, rng, engine=None):
+    """tbls.GenerateTSS ``count`` times in ONE engine call: a list of (TSS,
+    shares, secret), bit-identical to ``count`` sequential generate_tss calls
+    with the same seed (per item the secret is drawn, then its t - 1
+    coefficients).  Split, commitments and pubshares all on the fixed
+    schedule (split_secret_batch).  Raises generate_tss's TblsError."""
+    if not (2 <= t <= n <= 255):
+        raise TblsError("generate secret shares: new Feldman VSS: need 2 <= t <= n <= 255")
+    polys = []
+    for _ in range(int(count)):
+        secret = rng.randrange(1, R)
+        polys.append([secret] + [rng.randrange(1, R) for _ in range(t - 1)])
+    if not polys:
+        return []
+    out = []
+    for poly, r in zip(polys, _split_device(polys, n, _engine(engine))):
+        if isinstance(r, Exception):
+            raise TblsError("generate secret shares: " + str(r))
+        shares, commits, pks = r
+        out.append((TSS({s.identifier: PublicKey(pk) for s, pk in zip(shares, pks)}, n, t, PublicKey(commits[0]),
+                        tuple(commits)), shares, poly[0]))
+    return out
+
+
+def combine_shares_batch(sets, engine=None):
+    """tbls.CombineShares for many share sets in ONE launch on the fixed
+    schedule (tbg_combine_shares_ct): sets is a list of (shares, t, n).
+    combine_shares's host checks on public data run first, with its exact
+    strings; the sets that pass go out together.  Per set returns the secret
+    (int) or a TblsError: "combine shares: ..." for what the engine refuses (a
+    zero or out-of-range value), "unmarshal secret: ..." when the combined
+    secret is zero."""
+    res, good, slots = [], [], []
+    for k, (shares, t, n) in enumerate(sets):
+        shares = list(shares)
+        ids = [s.identifier for s in shares]
+        err = None
+        if not (2 <= t <= n <= 255):
+            err = "new Feldman VSS: need 2 <= t <= n <= 255"
+        elif len(shares) < t:
+            err = "combine shares: fewer shares than the threshold"
+        elif len(set(ids)) != len(ids):
+            err = "combine shares: duplicate share identifier"
+        elif any(i > n for i in ids):
+            err = "combine shares: invalid share identifier"
+        if err is None:
+            try:
+                good.append((ids, b"".join(_sk32_exact(s.value) for s in shares)))
+                slots.append(k)
+            except TblsError as e32:
+                err = "combine shares: " + str(e32).split(": ", 1)[-1]
+        res.append(TblsError(err) if err else None)
+    if good:
+        first = np.concatenate([[0], np.cumsum([len(ids) for ids, _ in good])]).astype(np.uint32)
+        out, st = _engine(engine).combine_shares_ct(b"".join(v for _, v in good), [i for ids, _ in good for i in ids], first)
+        for k, sec, s in zip(slots, out, st.tolist()):
+            res[k] = int.from_bytes(bytes(sec), "big") if s == eng.SH_OK else \
+                TblsError(_SH_COMBINE_ERRORS.get(s, f"combine shares: status {s}"))
+    return res

@@ -477,6 +477,78 @@ int tbg_sk_to_pk_ct(tbg_ctx* ctx, const uint8_t* sk32, uint32_t n, uint8_t* pk48
 int tbg_sign_ct(tbg_ctx* ctx, const uint8_t* sk32, uint32_t n, const uint8_t* msgs, const uint32_t* msg_off,
                 uint32_t n_msgs, const uint32_t* item_msg, uint8_t* sig96, int32_t* status);
 
+/* Shares on a fixed schedule: tbls.SplitSecret, GenerateTSS and CombineShares
+ * (reference tbls/tss.go:256-290, :120-139, :220-253; their callers
+ * cmd/createcluster.go:250-270, dkg/keycast.go:164-186,
+ * testutil/combine/main.go:83) -- the functions of tss.go that do arithmetic
+ * in Fr on secret values.  With these two calls every function of tss.go has
+ * an engine entry.
+ *
+ * tbg_split_secret_ct.  coef32 holds the 32-byte big-endian coefficients of
+ * n_polys polynomials; polynomial p owns [poly_first[p], poly_first[p + 1]),
+ * lowest first, coefficient 0 being the secret.  The CALLER draws the random
+ * coefficients (as kryptology does from its reader); the engine draws no
+ * randomness.  For n = n_shares and i = 1..n:
+ *   share32[p n + i - 1]    = f_p(i) mod r, 32 bytes big-endian
+ *   commit48[c]             = [coef_c] G1, compressed (Feldman commitments)
+ *   pubshare48[p n + i - 1] = [f_p(i)] G1, compressed (NULL: not formed)
+ * status[p] is the first of TBG_SH_COEF_ZERO / _COEF_RANGE by coefficient
+ * index, then TBG_SH_SHARE_ZERO (some f_p(i) == 0), otherwise TBG_SH_OK.  A
+ * failed polynomial has ALL its outputs zero and does not disturb the others.
+ * TBG_E_INVALID_ARG: a required pointer is NULL, poly_first[0] != 0,
+ * poly_first decreases, n_shares outside 1..255, a polynomial with fewer than
+ * 2 or more than n_shares coefficients (NewFeldman's rule), n_polys * n_shares
+ * >= 2^31.  n_polys == 0: TBG_OK, nothing is launched.
+ *
+ * tbg_combine_shares_ct.  Set k owns the shares [set_first[k], set_first[k + 1]):
+ * share_id[i] the public identifier, share32[i] the secret value.
+ *   secret32[k] = sum_i lambda_i s_i mod r, lambda_i = prod_(j != i) id_j / (id_j - id_i),
+ * interpolation at 0 over ALL shares given, as kryptology's Combine does; the
+ * threshold check (fewer shares than t) stays with the caller, which knows t.
+ * status[k], in this precedence: TBG_SH_TOO_FEW, _ID, _DUPLICATE_ID, then
+ * _VALUE_ZERO / _VALUE_RANGE (the first by index), then _SECRET_ZERO, otherwise
+ * TBG_SH_OK.  A failed set has secret32[k] zero.  TBG_E_INVALID_ARG: a
+ * required pointer is NULL, set_first[0] != 0, set_first decreases.
+ * n_sets == 0: TBG_OK, nothing is launched.
+ *
+ * The polynomial evaluation (Horner's rule, one lane per share) and the
+ * interpolation (one lane per set) run over csrc/bls_frct.h: Fr in masks and
+ * the operators + - * & | ^ ~ << >> alone.  The commitments and pubshares are
+ * the hardened signer's ladder above, run over the coefficients and over the
+ * shares (a zero share replaced by 1 by a mask select) where the split left
+ * them on the device: no share travels to the host between the split and its
+ * ladder.
+ * CLAIMED (the hardened signer's claims, and no wider): the instruction
+ * stream and the address stream (global memory, LDS, scratch) of the device
+ * code do not depend on a coefficient, a share, a share value or a combined
+ * secret; the host range check is the signer's word-wise compare with no early
+ * exit, and a refused polynomial or set goes to the device as ones, replaced
+ * by masks; secret outputs come back through pinned staging the engine owns
+ * and are copied to the caller from there; every device byte that held a
+ * coefficient, a share, a ladder scalar, a share value or a combined secret
+ * and every pinned staging buffer is overwritten with zeros on every exit path
+ * before it is released.
+ * Equal identifiers, set sizes and thresholds are public.
+ * NOT CLAIMED: power or electromagnetic leakage; isolation from other tenants
+ * of the device; that the multiply instructions take the same time for all
+ * operand values; the wiping of registers and of compiler-placed scratch; the
+ * caller's own copies of its inputs and outputs.  Which polynomial or set was
+ * refused, and why, is reported and therefore not hidden. */
+#define TBG_SH_OK 0
+#define TBG_SH_COEF_ZERO (-60)    /* a coefficient (the secret included) is 0        */
+#define TBG_SH_COEF_RANGE (-61)   /* a coefficient is >= r                           */
+#define TBG_SH_SHARE_ZERO (-62)   /* some f(i) == 0: that share is no SecretKeyShare */
+#define TBG_SH_TOO_FEW (-63)      /* combine: fewer than 2 shares in the set         */
+#define TBG_SH_ID (-64)           /* combine: an identifier is 0                     */
+#define TBG_SH_DUPLICATE_ID (-65) /* combine: identifiers collide                    */
+#define TBG_SH_VALUE_ZERO (-66)   /* combine: a share value is 0                     */
+#define TBG_SH_VALUE_RANGE (-67)  /* combine: a share value is >= r                  */
+#define TBG_SH_SECRET_ZERO (-68)  /* combine: the combined secret is 0               */
+int tbg_split_secret_ct(tbg_ctx* ctx, const uint8_t* coef32, const uint32_t* poly_first, uint32_t n_polys,
+                        uint32_t n_shares, uint8_t* share32, uint8_t* commit48, uint8_t* pubshare48, int32_t* status);
+int tbg_combine_shares_ct(tbg_ctx* ctx, const uint8_t* share32, const uint8_t* share_id, const uint32_t* set_first,
+                          uint32_t n_sets, uint8_t* secret32, int32_t* status);
+
 /* tbls.NewTSS / getPubShare (reference tbls/tss.go:95-116, :293-325) and the
  * right-hand side of Feldman share verification: commitment polynomials
  * evaluated in G1.  commit48 holds the 48-byte commitments C_j = [a_j] G1 of
