@@ -52,6 +52,12 @@ def is_stale():
     return any(os.path.getmtime(s) > t for s in list(sources()) + [os.path.abspath(__file__)])
 
 
+# What every device translation unit is compiled with and every device library
+# linked with: build() below, and the device unit harnesses of tests/twin_build.py.
+COMMON_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed", "-Wno-unused-result",
+                "-Wno-unused-value"]
+LINK_FLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC"]
+
 # Per-translation-unit compiler flags on top of the common ones.  The
 # machine scheduler's max-ILP strategy for the decode and Miller units
 # (k_decode_sigs -3 %, k_miller_hex<L0> -2 % with unchanged occupancy;
@@ -84,8 +90,7 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 0, defines=(),
         tag = os.path.basename(os.path.dirname(os.path.abspath(target))) + "_" + tag
     objdir = os.path.join(PKG, "build_obj", tag)
     os.makedirs(objdir, exist_ok=True)
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed", "-Wno-unused-result", "-Wno-unused-value"]
-    flags += ["-D" + d for d in defines] + list(extra_flags)
+    flags = COMMON_FLAGS + ["-D" + d for d in defines] + list(extra_flags)
 
     unit_flags = UNIT_FLAGS if unit_flags is None else unit_flags
     stamp_text = " ".join(flags) + "".join(f" [{u}: {' '.join(f)}]" for u, f in sorted(unit_flags.items()))
@@ -121,7 +126,7 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 0, defines=(),
         check_return_address(obj)
     with open(stamp, "w") as f:
         f.write(stamp_text)
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + list(link_flags) + objs + ["-o", target + ".tmp"]
+    cmd = [hipcc] + LINK_FLAGS + list(link_flags) + objs + ["-o", target + ".tmp"]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)

@@ -15,98 +15,14 @@ with k_decode.hip for dc_decode_sigs / dc_decode_pubkeys.  The library
 therefore defines tbg::launch_hash_msgs, tbg::launch_decode_sigs and the
 kernels' host stubs under the product's names:
 it is linked with devcheck.map (only dc_* exported, everything else local)
-and -Bsymbolic, and build() refuses a library that exports a tbg:: symbol, so
+and -Bsymbolic, and the build refuses a library that exports a tbg:: symbol, so
 libdevcheck.so and libtbls_gpu.so each call their own code when both are
-loaded in one process, in either order.
+loaded in one process, in either order.  (The sources, their product units
+and the build itself: tests/twin_build.py.)
 """
 import ctypes
-import os
-import subprocess
-import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-# devcheck.hip: the field layer; devcheck_g2.hip: the lane-pair G2 group law,
-# a source of its own because it is compiled as k_sgb.hip compiles that code
-# (TBG_ADD_DBL_INLINE / TBG_SCHED_FENCE set before the product headers)
-# devcheck_h2c.hip / devcheck_h2c_clear.hip: the hash-to-G2 chain, one source
-# per product unit they include (INCLUDES: the flags of _native.UNIT_FLAGS
-# follow the included unit)
-# devcheck_decode.hip: the decode kernels, k_decode.hip included the same way
-SRCS = [os.path.join(HERE, f) for f in ("devcheck.hip", "devcheck_g2.hip", "devcheck_h2c.hip",
-                                        "devcheck_h2c_clear.hip", "devcheck_decode.hip")]
-INCLUDES = {"devcheck_h2c.hip": "k_hash.hip", "devcheck_h2c_clear.hip": "k_hash_clear.hip",
-            "devcheck_decode.hip": "k_decode.hip"}
-LIB = os.path.join(HERE, "libdevcheck.so")
-MAP = os.path.join(HERE, "devcheck.map")
-CSRC = os.path.join(os.path.dirname(os.path.dirname(HERE)), "charon_amd", "csrc")
-
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed", "-Wno-unused-result",
-         "-Wno-unused-value"]
-
-# seconds the last build() spent compiling (None: the library was up to date)
-LAST_BUILD_SECONDS = None
-
-
-def _stale():
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    from charon_amd import _native
-    deps = SRCS + [MAP, os.path.abspath(__file__), os.path.abspath(_native.__file__)]  # (the last two hold the flags)
-    deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    deps += [os.path.join(CSRC, u) for u in INCLUDES.values()]
-    return any(os.path.getmtime(d) > t for d in deps)
-
-
-def unit_flags(src):
-    """The per-unit flags of the product unit `src` includes (none for the
-    sources that include headers only)."""
-    from charon_amd import _native
-    return list(_native.UNIT_FLAGS.get(INCLUDES.get(os.path.basename(src), ""), ()))
-
-
-def _check_exports(lib):
-    """Only the dc_* entries may be visible to the dynamic linker (see the
-    module docstring)."""
-    objdump = "/opt/rocm/llvm/bin/llvm-objdump"
-    if not os.path.exists(objdump):
-        raise RuntimeError(f"{objdump} is missing: cannot check the exports of {lib}")
-    out = subprocess.run([objdump, "-T", lib], capture_output=True, text=True, check=True).stdout
-    rows = [l.split() for l in out.splitlines() if l[:1].isalnum() and l.split()[0].strip("0123456789abcdef") == ""]
-    defined = [r[-1] for r in rows if "*UND*" not in r]
-    if not any(s == "dc_h2c" for s in defined):
-        raise RuntimeError(f"{lib}: dc_h2c not among the dynamic symbols {defined[:5]}")
-    bad = [s for s in defined if not s.startswith("dc_")]
-    if bad:
-        raise RuntimeError(f"{lib} exports {bad[:5]} ({len(bad)} symbols besides dc_*): these could bind across "
-                           "libtbls_gpu.so")
-
-
-def build():
-    """Compile the devcheck sources for gfx950 if the library is stale; raises
-    without hipcc."""
-    global LAST_BUILD_SECONDS
-    if _stale():
-        from charon_amd import _native
-        hipcc = _native._hipcc()  # raises: a stale library is an error, never a skip
-        t0 = time.time()
-        from concurrent.futures import ThreadPoolExecutor
-        objs = [os.path.splitext(src)[0] + ".o" for src in SRCS]
-        with ThreadPoolExecutor(max_workers=len(SRCS)) as ex:
-            list(ex.map(lambda so: subprocess.check_call([hipcc] + FLAGS + unit_flags(so[0]) +
-                                                         ["-c", so[0], "-o", so[1]]),
-                        zip(SRCS, objs)))
-        for obj in objs:
-            _native.check_return_address(obj)
-        subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-Bsymbolic",
-                               "-Wl,--version-script=" + MAP] + objs + ["-o", LIB + ".tmp"])
-        _check_exports(LIB + ".tmp")
-        os.replace(LIB + ".tmp", LIB)
-        LAST_BUILD_SECONDS = time.time() - t0
-    return LIB
-
-
-_lib = None
+from tests import twin_build
 
 _U32P = ctypes.POINTER(ctypes.c_uint32)
 _I32P = ctypes.POINTER(ctypes.c_int32)
@@ -157,13 +73,18 @@ H2C_STAGES = ["MAP_MSG", "MAP_U", "SSWU", "CLEAR_X1", "CLEAR_X2", "CLEAR_FIN", "
 DECODE_STAGES = ["DECODE", "SUBGROUP"]
 
 
+def _signatures(L):
+    for name, args in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = args
+
+
+def build():
+    """Compile the devcheck sources for gfx950 if the library is stale; raises
+    without hipcc."""
+    return twin_build.build("devcheck")
+
+
 def lib():
-    global _lib
-    if _lib is None:
-        L = ctypes.CDLL(build())
-        for name, args in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = ctypes.c_int
-            fn.argtypes = args
-        _lib = L
-    return _lib
+    return twin_build.lib("devcheck", _signatures)

@@ -7,37 +7,12 @@ or limb bound of the lazy sums (as tests/hostcheck does for the rest of the
 device math).
 """
 import ctypes
-import os
-import subprocess
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "hlines_host.cpp")
-LIB = os.path.join(HERE, "libhlines_host.so")
-CSRC = os.path.join(os.path.dirname(os.path.dirname(HERE)), "charon_amd", "csrc")
+from tests import twin_build
 
 N_LINES = 68
 LINE_WORDS = 3 * 2 * 14
 LINES_WORDS = N_LINES * LINE_WORDS
-
-
-def _stale():
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    deps = [SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    return any(os.path.getmtime(d) > t for d in deps)
-
-
-def build():
-    if _stale():
-        cxx = "/opt/rocm/llvm/bin/clang++"
-        if not os.path.exists(cxx):
-            cxx = "clang++"
-        tmp = LIB + ".%d.tmp" % os.getpid()
-        subprocess.check_call([cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-DTBG_BOUNDS_CHECK",
-                               "-Wno-pass-failed", SRC, "-o", tmp])
-        os.replace(tmp, LIB)
-    return LIB
 
 
 def aff192(q):
@@ -56,19 +31,19 @@ def h_of(msg):
     return (b2f(out.raw[:96]), b2f(out.raw[96:]))
 
 
-_lib = None
+def _signatures(h):
+    c, i, u, p = ctypes.c_char_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p
+    for name, args in {"hl_hash": [c, u, c], "hl_steps": [c, i, c, c, c], "hl_words": [c, p],
+                       "hl_pairing": [c, c, i, c], "hl_verify": [c, c, u, c]}.items():
+        fn = getattr(h, name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = args
+    h.hl_words.restype = None
+
+
+def build():
+    return twin_build.build("hlines")
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        h = ctypes.CDLL(build())
-        c, i, u, p = ctypes.c_char_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p
-        for name, args in {"hl_hash": [c, u, c], "hl_steps": [c, i, c, c, c], "hl_words": [c, p],
-                           "hl_pairing": [c, c, i, c], "hl_verify": [c, c, u, c]}.items():
-            fn = getattr(h, name)
-            fn.restype = ctypes.c_int
-            fn.argtypes = args
-        h.hl_words.restype = None
-        _lib = h
-    return _lib
+    return twin_build.lib("hlines", _signatures)

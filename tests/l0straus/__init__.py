@@ -6,48 +6,23 @@ clang (host target) and TBG_BOUNDS_CHECK, which aborts on any violated value
 bound (as tests/hostcheck does for the rest of the device math).
 """
 import ctypes
-import os
-import subprocess
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "l0straus_host.cpp")
-LIB = os.path.join(HERE, "libl0straus_host.so")
-CSRC = os.path.join(os.path.dirname(os.path.dirname(HERE)), "charon_amd", "csrc")
+from tests import twin_build
 
 
-def _stale():
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    deps = [SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    return any(os.path.getmtime(d) > t for d in deps)
+def _signatures(h):
+    p, i = ctypes.c_void_p, ctypes.c_int
+    h.ls_digits.restype = None
+    h.ls_digits.argtypes = [p, ctypes.c_uint32, p]
+    h.ls_duty.restype = i
+    h.ls_duty.argtypes = [ctypes.c_char_p, i, p, p, p, i, i, ctypes.POINTER(i), ctypes.c_char_p]
+    h.ls_reference.restype = i
+    h.ls_reference.argtypes = [ctypes.c_char_p, i, p, p, p, i, ctypes.c_char_p]
 
 
 def build():
-    if _stale():
-        cxx = "/opt/rocm/llvm/bin/clang++"
-        if not os.path.exists(cxx):
-            cxx = "clang++"
-        tmp = LIB + ".%d.tmp" % os.getpid()
-        subprocess.check_call([cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-DTBG_BOUNDS_CHECK",
-                               "-Wno-pass-failed", SRC, "-o", tmp])
-        os.replace(tmp, LIB)
-    return LIB
-
-
-_lib = None
+    return twin_build.build("l0straus")
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        h = ctypes.CDLL(build())
-        p, i = ctypes.c_void_p, ctypes.c_int
-        h.ls_digits.restype = None
-        h.ls_digits.argtypes = [p, ctypes.c_uint32, p]
-        h.ls_duty.restype = i
-        h.ls_duty.argtypes = [ctypes.c_char_p, i, p, p, p, i, i, ctypes.POINTER(i), ctypes.c_char_p]
-        h.ls_reference.restype = i
-        h.ls_reference.argtypes = [ctypes.c_char_p, i, p, p, p, i, ctypes.c_char_p]
-        _lib = h
-    return _lib
+    return twin_build.lib("l0straus", _signatures)

@@ -7,59 +7,33 @@ TEST TOOLING ONLY -- see plan_host.cpp.  Built on demand with the ROCm clang
 headers' types.
 """
 import ctypes
-import os
-import subprocess
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "plan_host.cpp")
-LIB = os.path.join(HERE, "libplan_host.so")
-CSRC = os.path.join(os.path.dirname(os.path.dirname(HERE)), "charon_amd", "csrc")
+from tests import twin_build
 
 
-def _stale():
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    deps = [SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    return any(os.path.getmtime(d) > t for d in deps)
+def _signatures(h):
+    p, i, u, q, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double
+    h.pl_max_sections.restype = u
+    h.pl_max_sections.argtypes = []
+    h.pl_layout.restype = i
+    h.pl_layout.argtypes = [p, u, q, p, u, p, u, p, p, p, p]
+    h.pl_bind.restype = i
+    h.pl_bind.argtypes = [p, u, q, p, u, p, u, q, q, q, p, p, p]
+    h.pl_shape_fits.restype = i
+    h.pl_shape_fits.argtypes = [u, u, u, u, u, u]
+    h.pl_l0_shape.restype = None
+    h.pl_l0_shape.argtypes = [q, u, i, u, u, u, u, p, u, p]
+    h.pl_sgb_plan.restype = i
+    h.pl_sgb_plan.argtypes = [d, p]
+    h.pl_max_work_sections.restype = u
+    h.pl_max_work_sections.argtypes = []
+    h.pl_work.restype = i
+    h.pl_work.argtypes = [u, p, q, p, p, p, p]
 
 
 def build():
-    if _stale():
-        rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-        cxx = os.path.join(rocm, "llvm", "bin", "clang++")
-        if not os.path.exists(cxx):
-            cxx = "clang++"
-        tmp = LIB + ".%d.tmp" % os.getpid()
-        subprocess.check_call([cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__",
-                               "-I" + os.path.join(rocm, "include"), "-Wno-pass-failed", SRC, "-o", tmp])
-        os.replace(tmp, LIB)
-    return LIB
-
-
-_lib = None
+    return twin_build.build("plan")
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        h = ctypes.CDLL(build())
-        p, i, u, q, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double
-        h.pl_max_sections.restype = u
-        h.pl_max_sections.argtypes = []
-        h.pl_layout.restype = i
-        h.pl_layout.argtypes = [p, u, q, p, u, p, u, p, p, p, p]
-        h.pl_bind.restype = i
-        h.pl_bind.argtypes = [p, u, q, p, u, p, u, q, q, q, p, p, p]
-        h.pl_shape_fits.restype = i
-        h.pl_shape_fits.argtypes = [u, u, u, u, u, u]
-        h.pl_l0_shape.restype = None
-        h.pl_l0_shape.argtypes = [q, u, i, u, u, u, u, p, u, p]
-        h.pl_sgb_plan.restype = i
-        h.pl_sgb_plan.argtypes = [d, p]
-        h.pl_max_work_sections.restype = u
-        h.pl_max_work_sections.argtypes = []
-        h.pl_work.restype = i
-        h.pl_work.argtypes = [u, p, q, p, p, p, p]
-        _lib = h
-    return _lib
+    return twin_build.lib("plan", _signatures)

@@ -11,20 +11,16 @@ One Fp multiplication = 392 u32 mul-adds in this radix-2^28 schedule
 import ctypes
 import json
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-SRC = os.path.join(ROOT, "tests", "hostcheck", "hostcheck.cpp")
-LIB = os.path.join(ROOT, "tests", "hostcheck", "libhostcheck_count.so")
+from tests import twin_build  # noqa: E402  (the TBG_COUNT_OPS builds are entries of its table)
 L0_DUTY_PARTIALS = 600000  # include/tbls_gpu.h TBG_L0_DUTY_PARTIALS
 
 
 def main():
-    subprocess.check_call(["/opt/rocm/llvm/bin/clang++", "-O1", "-std=c++17", "-fPIC", "-shared", "-DTBG_COUNT_OPS",
-                           "-Wno-pass-failed", SRC, "-o", LIB])
-    lib = ctypes.CDLL(LIB)
+    lib = twin_build.lib("hostcheck_count")
     lib.hc_count_get.restype = ctypes.c_ulonglong
     gold = json.load(open(os.path.join(ROOT, "tests", "golden", "cfg1_3of4_single.json")))["vectors"][0]
     msg = bytes.fromhex(gold["msg"])
@@ -50,11 +46,7 @@ def main():
     # l1 and l4 stored unevaluated.  Probe: tests/hlines/hlines_host.cpp built
     # with TBG_COUNT_OPS, both lanes of the pair counted.  (The signature side
     # keeps the Jacobian steps: lines_sig above.)
-    hsrc = os.path.join(ROOT, "tests", "hlines", "hlines_host.cpp")
-    hlib_path = os.path.join(ROOT, "tests", "hlines", "libhlines_count.so")
-    subprocess.check_call(["/opt/rocm/llvm/bin/clang++", "-O1", "-std=c++17", "-fPIC", "-shared", "-DTBG_COUNT_OPS",
-                           "-Wno-pass-failed", hsrc, "-o", hlib_path])
-    hlib = ctypes.CDLL(hlib_path)
+    hlib = twin_build.lib("hlines_count")
     hlib.hl_count_get.restype = ctypes.c_ulonglong
     h_aff = ctypes.create_string_buffer(192)
     assert hlib.hl_hash(msg, len(msg), h_aff) == 0
@@ -88,11 +80,7 @@ def main():
     # TBG_COUNT_OPS counts one line product over the six lanes in either form; every line product of a
     # measured chunk is corrected by the difference (miller_chunk below: 68 lines per duty pair and for
     # the folded S).
-    xsrc = os.path.join(ROOT, "tests", "hexline", "hexline_host.cpp")
-    xlib_path = os.path.join(ROOT, "tests", "hexline", "libhexline_count.so")
-    subprocess.check_call(["/opt/rocm/llvm/bin/clang++", "-O1", "-std=c++17", "-fPIC", "-shared", "-DTBG_COUNT_OPS",
-                           "-Wno-pass-failed", xsrc, "-o", xlib_path])
-    xlib = ctypes.CDLL(xlib_path)
+    xlib = twin_build.lib("hexline_count")
     xlib.hxl_hc_count.restype = ctypes.c_ulonglong
     line_direct, line_kara = xlib.hxl_hc_count(0), xlib.hxl_hc_count(1)
     assert line_direct == 6 * 2 * 7 * 196 and line_kara - line_direct == 6 * (196 + 2 * 14), (line_direct, line_kara)
@@ -209,11 +197,7 @@ def main():
     # TBG_L0_TAIL_PARTIALS partials, the S role of k_rlc_g1_l0's own grid, a
     # per-launch term of that kernel; k_l0f_* in smaller launches.  Probes:
     # tests/l0fused/l0fused_host.cpp built with TBG_COUNT_OPS.
-    fsrc = os.path.join(ROOT, "tests", "l0fused", "l0fused_host.cpp")
-    flib_path = os.path.join(ROOT, "tests", "l0fused", "libl0fused_count.so")
-    subprocess.check_call(["/opt/rocm/llvm/bin/clang++", "-O1", "-std=c++17", "-fPIC", "-shared", "-DTBG_COUNT_OPS",
-                           "-Wno-pass-failed", fsrc, "-o", flib_path])
-    flib = ctypes.CDLL(flib_path)
+    flib = twin_build.lib("l0fused_count")
     flib.l0f_hc_count_get.restype = ctypes.c_ulonglong
 
     def fmeasure(fn, *a):
@@ -236,11 +220,7 @@ def main():
     # conversion k_rlc_duty_sum<DSUM_L0_P> ran.  Probes: tests/l0straus/
     # l0straus_host.cpp built with TBG_COUNT_OPS, four distinct keys and the
     # digit sets above (7-of-10: ten candidates, keys repeating with other digits).
-    ssrc = os.path.join(ROOT, "tests", "l0straus", "l0straus_host.cpp")
-    slib_path = os.path.join(ROOT, "tests", "l0straus", "libl0straus_count.so")
-    subprocess.check_call(["/opt/rocm/llvm/bin/clang++", "-O1", "-std=c++17", "-fPIC", "-shared", "-DTBG_COUNT_OPS",
-                           "-Wno-pass-failed", ssrc, "-o", slib_path])
-    slib = ctypes.CDLL(slib_path)
+    slib = twin_build.lib("l0straus_count")
     slib.ls_count_get.restype = ctypes.c_ulonglong
     assert slib.ls_probe_setup(b"".join(pks), len(pks)) == 0
 
