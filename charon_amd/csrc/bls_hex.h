@@ -230,6 +230,16 @@ TBG_HD bool hx_is_one_lane(uint32_t c, int q, const Fp4h& A) {
   return fp_is_zero(A.b) && ((q == 0 && c == 0) ? a_one : a_zero);
 }
 
+// Fp12 slot of global thread t (UINT32_MAX for lane 15 of a row), the
+// threads n slots need and the slots a grid of `threads` holds (the stride of
+// a hexad kernel that loops over a list, fb_pass_loop): 10 per wave.
+TBG_HD uint32_t hex_slot(uint32_t t) {
+  const uint32_t l = t & 15u;
+  return l == 15u ? 0xFFFFFFFFu : (t >> 6) * 10u + ((t >> 5) & 1u) * 5u + l / 3u;
+}
+inline uint32_t hex_threads(uint32_t n) { return 64u * ((n + 9u) / 10u); }
+TBG_HD uint32_t hex_slots_of(uint32_t threads) { return threads / 64u * 10u; }
+
 }  // namespace tbg
 
 // ---------------------------------------------------------------------------
@@ -243,18 +253,13 @@ namespace tbg {
 // per word.  (Halves of the wave with v_permlane32_swap took a copy and a
 // per-half select besides -- 3 VALU instructions per word; measured slower,
 // round 4: profiles/r04/lazy/; removed.)
-// Fp12 slot of global thread t (UINT32_MAX for lane 15 of a row), and the
-// threads n slots need: 10 per wave.
-TBG_HD uint32_t hex_slot(uint32_t t) {
-  const uint32_t l = t & 15u;
-  return l == 15u ? 0xFFFFFFFFu : (t >> 6) * 10u + ((t >> 5) & 1u) * 5u + l / 3u;
-}
-inline uint32_t hex_threads(uint32_t n) { return 64u * ((n + 9u) / 10u); }
 TBG_DEV uint32_t hex_c() { return (threadIdx.x >> 4) & 1u; }
 // lane (q, c) = (0, 0) of this thread's hexad: the one that takes list slots
 // and writes per-entry verdicts
 TBG_DEV bool hex_lead() { return quad_lane() == 0 && hex_c() == 0; }
 TBG_DEV uint32_t hex_lead_lane() { return (threadIdx.x - (uint32_t)quad_lane()) & ~16u; }
+// the slots of the running grid
+TBG_DEV uint32_t hex_grid_slots() { return gridDim.x * hex_slots_of(blockDim.x); }
 // hexad kernels fit 256 VGPRs: two waves per SIMD
 #ifndef TBG_HEX_WAVES
 #define TBG_HEX_WAVES 2

@@ -52,7 +52,7 @@ __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_lines_fold(DevBatch B) {
                          : KIND == FOLD_CID  ? B.counters[CNT_CID]
                          : KIND == FOLD_GID  ? B.counters[CNT_GID]
                                              : B.counters[CNT_DUTIES];
-  fb_pass_loop(B, pr, (gridDim.x * blockDim.x) >> 1, count, [&](uint32_t k) { lines_fold_one<KIND>(B, k); });
+  fb_pass_loop(B, pr, pair_slots_of(gridDim.x * blockDim.x), count, [&](uint32_t k) { lines_fold_one<KIND>(B, k); });
 }
 
 void launch_lines_fold(const DevBatch& B, int kind, uint32_t max_entries, hipStream_t st) {

@@ -591,8 +591,7 @@ __global__ void TBG_LAUNCH_N(TBG_HEX_WAVES) k_rlc_ident_check(DevBatch B) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (hex_slot(t) == 0xFFFFFFFFu) return;
   const bool lead = hex_lead();
-  const uint32_t per = (gridDim.x * (blockDim.x / 64u) * 10u);
-  fb_pass_loop(B, hex_slot(t), per, B.counters[CNT_DUTIES], [&](uint32_t k) {
+  fb_pass_loop(B, hex_slot(t), hex_grid_slots(), B.counters[CNT_DUTIES], [&](uint32_t k) {
   const uint32_t entry = B.id_list[k], d = entry & ~ID_DEGENERATE;
   uint32_t found = 0;
   if (!(entry & ID_DEGENERATE)) {
@@ -805,7 +804,7 @@ __global__ void TBG_LAUNCH k_list_all_partials(DevBatch B, const int32_t* pk_sta
 // at 1 % invalid against 1.4 ms, profiles/r04/merge/.)
 __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_lines_sig_list(DevBatch B) {
   // (pair-uniform branches; a grid smaller than the pass loops: fb_pass_loop)
-  fb_pass_loop(B, (blockIdx.x * blockDim.x + threadIdx.x) >> 1, (gridDim.x * blockDim.x) >> 1,
+  fb_pass_loop(B, (blockIdx.x * blockDim.x + threadIdx.x) >> 1, pair_slots_of(gridDim.x * blockDim.x),
                B.counters[CNT_PARTIALS], [&](uint32_t k) {
     const uint32_t i = B.part_list[k];
     const Fp nx = fp_reduce(fp_neg(fp_from_const(G1_X)));
@@ -816,9 +815,7 @@ __global__ void TBG_LAUNCH_N(TBG_PAIR_WAVES) k_lines_sig_list(DevBatch B) {
 }
 
 // Level 3 check: one hexad per listed partial, the exact CoreVerify.
-// (grid-stride over the pass: hexad slots per grid = 10 per wave)
-TBG_DEV uint32_t hex_grid_slots() { return gridDim.x * (blockDim.x / 64u) * 10u; }
-
+// (grid-stride over the pass)
 __global__ void TBG_LAUNCH_N(TBG_HEX_WAVES) k_verify_list(DevBatch B, const G1A* pk_aff) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (hex_slot(t) == 0xFFFFFFFFu) return;
@@ -839,23 +836,6 @@ __global__ void TBG_LAUNCH_N(TBG_HEX_WAVES) k_verify_list(DevBatch B, const G1A*
     const bool ok = hex_is_one(f);
     if (lead) B.partial_status[i] = ok ? TBG_PS_VALID : TBG_PS_INVALID;
   });
-}
-
-// The fallback levels' list positions [0, max_entries) in passes of
-// B.fb_window (the line buffer's capacity; 0: one pass), in stream order.
-// body(P, n): n = the list positions the pass's grids cover -- all of the
-// pass below B.fb_full, else FB_SMALL (the pass kernels that may run small
-// loop over the rest: fb_pass_loop; the others take n = the pass).
-constexpr uint32_t FB_SMALL = 640;  // 64 hexad waves, 20 pair waves
-template <class F>
-static void fb_passes(const DevBatch& B, uint32_t max_entries, F&& body, bool may_shrink = false) {
-  const uint32_t W = B.fb_window ? B.fb_window : max_entries;
-  for (uint32_t base = 0; base < max_entries; base += W) {
-    DevBatch P = B;
-    P.fb_base = base;
-    const uint32_t n = max_entries - base < W ? max_entries - base : W;
-    body(P, may_shrink && base > 0 && base >= B.fb_full && n > FB_SMALL ? FB_SMALL : n);  // (pass 0 always full)
-  }
 }
 
 void launch_rlc_prepare(const DevBatch& B, const G1A* pk_aff, const G1A* pk_tab, const int32_t* pk_status,

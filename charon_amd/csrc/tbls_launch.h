@@ -449,6 +449,25 @@ TBG_HD void fb_pass_loop(const DevBatch& B, uint32_t first, uint32_t stride, uin
     body(k);
   }
 }
+// The list positions a grid of `threads` holds at one lane pair each: the
+// stride of a pair kernel that loops (the hexad kernels': hex_slots_of, bls_hex.h).
+TBG_HD uint32_t pair_slots_of(uint32_t threads) { return threads >> 1; }
+// The fallback levels' list positions [0, max_entries) in passes of
+// B.fb_window (the line buffer's capacity; 0: one pass), in stream order.
+// body(P, n): n = the list positions the pass's grids cover -- all of the
+// pass below B.fb_full, else FB_SMALL (the pass kernels that may run small
+// loop over the rest: fb_pass_loop; the others take n = the pass).
+constexpr uint32_t FB_SMALL = 640;  // 64 hexad waves, 20 pair waves
+template <class F>
+inline void fb_passes(const DevBatch& B, uint32_t max_entries, F&& body, bool may_shrink = false) {
+  const uint32_t W = B.fb_window ? B.fb_window : max_entries;
+  for (uint32_t base = 0; base < max_entries; base += W) {
+    DevBatch P = B;
+    P.fb_base = base;
+    const uint32_t n = max_entries - base < W ? max_entries - base : W;
+    body(P, may_shrink && base > 0 && base >= B.fb_full && n > FB_SMALL ? FB_SMALL : n);  // (pass 0 always full)
+  }
+}
 
 // Participation of a partial in its duty's aggregate.  SPEC: the
 // speculative aggregation that runs BEFORE verification while level 0 is on

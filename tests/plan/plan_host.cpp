@@ -1,11 +1,15 @@
 // TEST TOOLING ONLY: C entry points over charon_amd/csrc/tbls_plan.h -- the
 // launch plan, the section layout, bind over fake base addresses and the
 // replay fit rule -- and over tbls_work.h, the workspaces of the one-shot
-// calls, for tests/test_plan_host.py.  Plain host C++: the headers make no
-// HIP runtime call.
+// calls, for tests/test_plan_host.py; and over the fallback lists' pass
+// schedule and grid-stride loops (tbls_launch.h fb_passes / fb_pass_loop, the
+// slot geometry of bls_hex.h), for tests/test_fb_passes_host.py.  Plain host
+// C++: the headers make no HIP runtime call.
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <vector>
+#include "../../charon_amd/csrc/bls_hex.h"
 #include "../../charon_amd/csrc/tbls_plan.h"
 #include "../../charon_amd/csrc/tbls_work.h"
 
@@ -149,6 +153,75 @@ void pl_l0_shape(uint64_t nd, uint32_t n_simd, int g_free, uint32_t G, uint32_t 
 }
 
 int pl_sgb_plan(double rho, uint32_t* m) { return sgb_plan(rho, *m) ? 1 : 0; }
+
+uint32_t pl_fb_small() { return FB_SMALL; }
+uint32_t pl_lines_words() { return LINES_WORDS; }
+
+// The passes fb_passes makes over a fallback list of `count` entries (max_entries: what the launcher sizes the
+// passes by), each with the grid its launcher starts and every walker of that grid run through fb_pass_loop:
+//   kind 0, the hexad kernels (k_verify_list, k_rlc_ident_check): grid_for(hex_threads(n)) blocks of kBlock, a
+//           walker per hex_slot of its threads, stride hex_slots_of(threads);
+//   kind 1, the pair kernels (k_lines_sig_list, k_lines_fold): grid_for(2 n), a walker per t >> 1, stride
+//           pair_slots_of(threads).
+// passes[p][6]: base, n as the body received it, the stride, the walkers (distinct slots of the grid's threads), the
+// offset of the pass in trips, the largest fb_slot a walker formed; trips[]: the body's runs per walker, in slot
+// order; hits[max_entries]: visits per list position (the caller zeroes it); hit_pass[max_entries]: the pass of the
+// last one.  Returns the number of passes; -1: passes or trips would not fit; -2: the threads' slots are not 0, 1, ...
+// with 6 (2) threads each; -3: a visit outside [0, count).
+int pl_fb_cover(uint32_t fb_w, uint32_t fb_full, uint32_t count, uint32_t max_entries, int may_shrink, int kind,
+                uint64_t* passes, uint32_t max_passes, uint32_t* trips, uint64_t max_trips, uint32_t* hits,
+                uint32_t* hit_pass) {
+  DevBatch B;
+  memset(&B, 0, sizeof(B));
+  B.fb_window = fb_w;
+  B.fb_full = fb_full;
+  int n_passes = 0, err = 0;
+  uint64_t used = 0;
+  std::vector<uint32_t> seen;
+  fb_passes(B, max_entries, [&](const DevBatch& P, uint32_t n) {
+    if (err) return;
+    const uint32_t blocks = (kind == 0 ? grid_for(hex_threads(n)) : grid_for(2 * n)).x, threads = blocks * (uint32_t)kBlock;
+    // (as hex_grid_slots forms it on the device: per block)
+    const uint32_t stride = kind == 0 ? blocks * hex_slots_of((uint32_t)kBlock) : pair_slots_of(threads);
+    const uint32_t lanes = kind == 0 ? 6u : 2u;
+    if ((uint32_t)n_passes >= max_passes || used + threads > max_trips) {
+      err = -1;
+      return;
+    }
+    uint64_t max_slot = 0;
+    uint32_t walkers = 0;
+    seen.assign(threads, 0u);
+    for (uint32_t t = 0; t < threads; ++t) {
+      const uint32_t s = kind == 0 ? hex_slot(t) : t >> 1;
+      if (s == 0xFFFFFFFFu) continue;  // (lane 15 of a row: no hexad)
+      if (s >= threads) {
+        err = -2;
+        return;
+      }
+      if (seen[s]++) continue;  // one walker per slot: its lanes walk together
+      ++walkers;
+      uint32_t runs = 0;
+      fb_pass_loop(P, s, stride, count, [&](uint32_t k) {
+        ++runs;
+        if (k >= count || k >= max_entries) {
+          err = -3;
+          return;
+        }
+        ++hits[k];
+        hit_pass[k] = (uint32_t)n_passes;
+        max_slot = std::max<uint64_t>(max_slot, fb_slot(P, k));
+      });
+      trips[used + s] = runs;
+    }
+    for (uint32_t s = 0; s < threads; ++s)
+      if (seen[s] != (s < walkers ? lanes : 0u)) err = -2;
+    const uint64_t row[6] = {P.fb_base, n, stride, walkers, used, max_slot};
+    memcpy(passes + 6 * (size_t)n_passes, row, sizeof(row));
+    used += walkers;
+    ++n_passes;
+  }, may_shrink != 0);
+  return err ? err : n_passes;
+}
 
 uint32_t pl_max_work_sections() { return kMaxWorkSections; }
 
